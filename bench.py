@@ -16,6 +16,12 @@ Weak scaling: every rank walks its own R roots; replicas exchange gradients thro
 
     python bench.py [--gpus N --steps K --warmup W]              (N > 1: spawns its own N ranks, one per GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's launcher: same ranks)
+
+A plain run sets up, warms up, times the K steps and prints the line (with the figures derived from the timed region's
+own counters and events).  ``--full`` adds every leg behind the timed region: the 8 192-root continuity batch, the solo
+kernel events, the fresh-batch end-to-end figures, the strict-mode lines and the CPU baselines.  ``--dump-outputs DIR``
+writes what the last timed step computed (sampled rows of both tables and biases, sampled prepared D rows and G pairs)
+as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +63,9 @@ def parse():
     p.add_argument("--profile-every", type=int, default=3,
                    help="HIP events around every k-th walk launch of the timed region (an event pair costs ~6 us of stream bubble on "
                         "each side of every level_score_kernel launch; an odd k alternates between the D-mode and G-mode launches)")
+    p.add_argument("--full", action="store_true", help="also run every leg behind the timed region (continuity batch, solo kernel events, "
+                                                       "fresh batches, strict mode, CPU baselines); a plain run only times the steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (fixed, seeded samples)")
     return p.parse_args()
 
 
@@ -214,6 +223,36 @@ def pmc_same_run():
 
 def delta(c1, c0):
     return {k: c1[k] - c0[k] for k in c1}
+
+
+DUMP_TABLE_BYTES = 16 << 20  # rows of each embedding table sampled so that one table's sample is at most 16 MB ...
+DUMP_TABLE_ROWS = 1 << 16    # ... and at most this many rows (the bias samples: narrow tables)
+DUMP_PAIRS = 1 << 18         # prepared D rows / G pairs sampled
+
+
+def dump_outputs(eng, out_dir):
+    """What the last timed step computed, as a caller of the step receives it: both models' embeddings and biases after its
+    D and G passes, the D rows (center, neighbor, label) and the G pairs (node_1, node_2, reward) it prepared.  Fixed, seeded
+    samples (the same rows for the same arguments); values float32, node ids float64; well under 64 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, d = eng.n_node, eng.n_emb
+    rows = np.sort(np.random.RandomState(0).choice(n, min(n, DUMP_TABLE_ROWS, max(1, DUMP_TABLE_BYTES // (4 * d))), replace=False))
+    arrays = {}
+    for which, name in ((0, "gen"), (1, "dis")):
+        arrays[name + "_emb_rows"] = eng.get_embeddings(which)[rows]
+        arrays[name + "_bias_rows"] = eng.get_bias(which)[rows]
+
+    def sample(k):
+        return np.sort(np.random.RandomState(1).choice(k, DUMP_PAIRS, replace=False)) if k > DUMP_PAIRS else np.arange(k)
+    c, nb, lab = eng.get_d_data()
+    i = sample(len(c))
+    arrays.update(d_center=c[i].astype(np.float64), d_neighbor=nb[i].astype(np.float64), d_label=lab[i])
+    a, b, r = eng.get_g_data()
+    i = sample(len(a))
+    arrays.update(g_node_1=a[i].astype(np.float64), g_node_2=b[i].astype(np.float64), g_reward=r[i])
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def exchange_label(comm):
@@ -465,13 +504,15 @@ def main():
     c1 = eng.counters()
     c = delta(c1, c0)
     comm = eng.comm_stats() if world > 1 and not share_gpu else None
+    if args.dump_outputs and rank == 0:  # before any leg below changes the tables or the prepared data
+        dump_outputs(eng, args.dump_outputs)
 
-    # ---- behind the timed region (every rank takes part: the steps contain collectives) -------------------------
+    # ---- behind the timed region, --full only (every rank takes part: the steps contain collectives) ------------
     nxt = args.warmup + args.steps
     # (0) continuity with rounds 1-2: the same step over the 8 192-root sample those rounds benched (a subset of the resident
     #     roots: bench_roots takes a prefix of one seeded permutation), so that the numbers of all rounds stay comparable
     cont = None
-    if 0 < args.continuity_roots < R and world == 1:
+    if args.full and 0 < args.continuity_roots < R and world == 1:
         sub = workloads.bench_roots(rowptr, args.continuity_roots, rank, world, args.seed)
         slot_of = {int(r): i for i, r in enumerate(roots)}
         sub_slots = np.array([slot_of[int(r)] for r in sub], dtype=np.int32)
@@ -499,19 +540,21 @@ def main():
         nxt += 3 + args.steps
     # (1) the same kernel events with the profiled side-stream launches ISOLATED (they first wait for the main stream): the
     #     kernel alone on the chip.  Not part of the timed region: isolating a launch serialises that step.
-    eng.set_profiling_solo(True)
-    eng.set_profiling(args.profile_every)
-    c2 = eng.counters()
-    for i in range(nxt, nxt + args.overlap_steps):
-        step(i, head_start=False)  # (a head start would put the walks beside the D pass again: the launch has nothing to wait for yet)
-    barrier()
-    co = delta(eng.counters(), c2)
-    eng.set_profiling_solo(False)
-    nxt += args.overlap_steps
+    co = None
+    if args.full:
+        eng.set_profiling_solo(True)
+        eng.set_profiling(args.profile_every)
+        c2 = eng.counters()
+        for i in range(nxt, nxt + args.overlap_steps):
+            step(i, head_start=False)  # (a head start would put the walks beside the D pass again: the launch has nothing to wait for yet)
+        barrier()
+        co = delta(eng.counters(), c2)
+        eng.set_profiling_solo(False)
+        nxt += args.overlap_steps
     # (2) end to end for roots whose trees are NOT resident: build the BFS trees of a fresh batch of R roots on the GPU,
     #     then one step on them (an epoch over all N roots is a sequence of exactly this)
     e2e = None
-    if args.fresh_batches > 0 and not args.host_bfs:
+    if args.full and args.fresh_batches > 0 and not args.host_bfs:
         c3 = eng.counters()
         barrier()
         t3 = time.perf_counter()
@@ -572,7 +615,7 @@ def main():
         return b, gbs(b, cc["score_kernel_ms"])
 
     sc_bytes, achieved = k1(c)
-    _, achieved_ovl = k1(co)
+    _, achieved_ovl = k1(co) if co else (None, None)
     sc_launches = c["score_launches"]
     # The reference evaluates every hop's distribution from scratch (4k(d+2) + 4d + 12 per hop);
     # the engine evaluates each distinct (root, node) distribution of a launch once.
@@ -612,7 +655,7 @@ def main():
         kd_o = gbs(row_b * c["d_rows_timed"], c["d_opt_ms"])
     kd_s = gbs((48.0 * d + 36.0) * c["d_pairs_timed"], c["d_grad_ms"] + c["d_opt_ms"])
     # the same pass in the old call order (steps behind the timed region): the G-mode walks start later, the kernel runs (almost) alone
-    kd_g_solo = gbs((16.0 * d + 20.0) * co["d_pairs_timed"], co["d_grad_ms"]) if co.get("d_passes_timed") else None
+    kd_g_solo = gbs((16.0 * d + 20.0) * co["d_pairs_timed"], co["d_grad_ms"]) if co and co.get("d_passes_timed") else None
     kg_s = gbs((48.0 * d + 36.0) * c["g_pairs_timed"], c["g_grad_ms"] + c["g_opt_ms"])
     out = {
         "metric": "sampled_edges_per_sec",
@@ -660,8 +703,9 @@ def main():
                      "timed": "HIP events on the engine's stream around every level_score_kernel launch of every %s walk call of the timed region, "
                               "as it runs in production: the G-mode launches share the chip with the discriminator update on the other stream" % (
                                   "" if args.profile_every == 1 else "%d-th" % args.profile_every),
-                     "solo": {"achieved": achieved_ovl, "frac": frac(achieved_ovl), "launches": int(co["score_launches"]),
-                              "what": "%d further steps whose profiled side-stream launches first wait for the main stream (the kernel alone on the chip)" % args.overlap_steps},
+                     "solo": ({"achieved": achieved_ovl, "frac": frac(achieved_ovl), "launches": int(co["score_launches"]),
+                               "what": "%d further steps whose profiled side-stream launches first wait for the main stream (the kernel alone on the chip)" % args.overlap_steps}
+                              if co else None),
                      # the sampler as a WHOLE: the same algorithmic bytes over the whole walk launches (score + weights + advance +
                      # the small kernels around them), HIP events around the profiled launches -- the level glue is latency bound and
                      # moves few algorithmic bytes, so this fraction is about half the score kernel's
@@ -680,9 +724,10 @@ def main():
                          "d": dict({"kernel": "pair_grad16_kernel (+ count / segment / slot kernels when staged)", "staged": bool(staged), "achieved": kd_g, "frac": frac(kd_g), "step_achieved": kd_s, "step_frac": frac(kd_s),
                                     "pairs": int(c["d_pairs_timed"]), "grad_ms": c["d_grad_ms"], "passes": int(c["d_passes_timed"]),
                                     "timed": "as it runs in production: beside the G-mode walks" + ("" if args.no_g_head_start else ", which gg_prepare_g_begin starts before the pass"),
-                                    "without_head_start": {"achieved": kd_g_solo, "frac": frac(kd_g_solo), "passes": int(co.get("d_passes_timed", 0)),
-                                                           "what": "the %d steps behind the timed region, which run in the old call order: the G-mode walks start once the host has enqueued the pass, "
-                                                                   "so the gradient kernel has the chip (almost) to itself" % args.overlap_steps}},
+                                    "without_head_start": ({"achieved": kd_g_solo, "frac": frac(kd_g_solo), "passes": int(co.get("d_passes_timed", 0)),
+                                                            "what": "the %d steps behind the timed region, which run in the old call order: the G-mode walks start once the host has enqueued the pass, "
+                                                                    "so the gradient kernel has the chip (almost) to itself" % args.overlap_steps}
+                                                           if co else None)},
                                    **by_traffic("pair_grad16_kernel", c["d_grad_ms"], c["d_passes_timed"])),
                          "g": dict({"kernel": "path_grad_kernel (+ count / segment / slot kernels when staged): reads every path node once and emits one gradient row per node",
                                     "bytes_model": "8d + 16 per path node (row read + gradient row written)", "path_nodes": int(g_nodes),
@@ -757,12 +802,12 @@ def main():
         out["roofline"]["with_tree_build_edges_per_sec"] = sums[3] / e2e_dt
         out["config"]["with_tree_build_edges_per_sec"] = sums[3] / e2e_dt
         out["config"]["with_tree_build_s_per_batch"] = e2e_dt / args.fresh_batches
-    if world == 1 and not args.no_strict:
+    if args.full and world == 1 and not args.no_strict:
         out["strict_mode"] = strict_mode_line(ga, _lib)
         out["strict_mode_1m"] = strict_mode_at_scale(ga, _lib, n, rowptr, col, emb, roots[:2048], args.n_sample_gen, args.seed)
         out["config"]["pairs_per_sec_batching"] = ("d_step_pairs_per_sec / g_step_pairs_per_sec: one fused batch per pass (fast mode, SURVEY 8d 2(ii)); "
                                                    "the reference's batch-64 schedule on this graph: strict_mode_1m")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         bias = eng.get_bias(0)
         embg = eng.get_embeddings(0)
         v, sample = cpu_baseline(args, n, rowptr, col, embg, bias, roots, args.cpu_baseline_seconds)

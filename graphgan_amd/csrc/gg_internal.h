@@ -253,7 +253,9 @@ struct gg_ctx {
     // only, so it is built on the side stream right behind them (enqueue_path_slots, steps.hip) -- beside the reward kernels
     // of the main stream -- in buffers of its own (the discriminator pass uses sg_* at the same time); ev_slots_done orders the
     // gradient kernel behind it.
-    gg::DevBuf sgp_cnt, sgp_off, sgp_slot, sgp_list, sgp_tot, sgp_key, sgp_scan;
+    gg::DevBuf sgp_cnt, sgp_off, sgp_slot, sgp_list, sgp_tot, sgp_key, sgp_scan, sgp_hub;  // sgp_hub: rows of the hubs of that index
+    gg::DevBuf sg_hub, hub_acc;        // hub rows of the pass's own index; their 64-bit fixed-point gradient sums (steps.hip, HubAcc)
+    int64_t hub_cap = 0;               // hubs hub_acc holds
     hipEvent_t ev_slots_done = nullptr;
     bool g_slots_ready = false;        // the index of the resident G-mode walks is enqueued / done
     bool sgp_cnt_clean = false;        // sgp_cnt is all zero
@@ -262,7 +264,7 @@ struct gg_ctx {
     int32_t g_slots_stride = 0;
     int32_t *sg_cnt_active = nullptr;  // the count array of the staged pass that is applying its hub rows (sg_active)
     bool sg_active = false;            // a staged G pass is applying its hub rows (apply_optimizer resets their counts)
-    int sg_threshold = 64;             // GG_STAGE_T: rows with more staged gradients than this keep the atomic path; 0 = everything atomic
+    int sg_threshold = 64;             // GG_STAGE_T: rows with more staged gradients than this are hubs (fixed-point sums); 0 = everything atomic
 
     // device-side counters of the walk launch in flight (zeroed at its start): [0]=hops [1]=nbr_reads [3]=error flag
     // [4]=ticket [5]=rows scored by the finisher; per-level and spread words from [8] on (walk_sample.hip)

@@ -18,11 +18,28 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "gg_internal.h"
 
 namespace gg {
+
+// STAGED passes: the gradient rows of a hub row (more than T staged gradients, no stage segment) are added as 64-bit
+// fixed-point integers, hub h at acc[h * (ld + 1)] (bias last), so their sum does not depend on the order the atomics
+// arrive in; hub_finalize_kernel turns them into the fp32 accumulators before the optimizer.  A slot <= -3 names hub -3 - slot.
+struct HubAcc {
+    unsigned long long *acc;
+    int64_t cap;   // hubs the buffer holds (a slot naming a hub beyond it keeps the fp32 atomics)
+    float scale;   // power of two: fixed-point units per gradient unit of this pass
+};
+__device__ __forceinline__ unsigned long long *hub_row(const HubAcc &h, int slot, int ld) {
+    const int64_t k = -3 - (int64_t)slot;
+    return (slot <= -3 && k < h.cap) ? h.acc + k * (ld + 1) : nullptr;
+}
+__device__ __forceinline__ void hub_add(unsigned long long *p, float x, float scale) {
+    atomicAdd(p, (unsigned long long)__float2ll_rn(x * scale));
+}
 
 struct StepArgs {
     float *E, *b;          // variables
@@ -41,6 +58,7 @@ struct StepArgs {
     // the u-side gradient of the run that ends at pair p (-2: no run ends there); -1 = hub row, atomics as before
     const int32_t *slot_v, *slot_u;
     float *stage, *stage_b;
+    HubAcc hub;
 };
 
 // occurrences of every table row in a fused batch, as the gradient kernel will emit them: one per pair for v, one per
@@ -61,11 +79,11 @@ __global__ __launch_bounds__(256) void pair_occ_slot_kernel(const int32_t *u, co
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const int iv = v[p], iu = u[p];
-    const int sv = cnt[iv] <= T ? off[iv] + slot_v[p] : -1;
+    const int sv = cnt[iv] <= T ? off[iv] + slot_v[p] : -3 - off[iv];
     slot_v[p] = sv;
     if (sv >= 0) key[sv] = 2 * p + 1;
     if (slot_u[p] != -2) {
-        const int su = cnt[iu] <= T ? off[iu] + slot_u[p] : -1;
+        const int su = cnt[iu] <= T ? off[iu] + slot_u[p] : -3 - off[iu];
         slot_u[p] = su;
         if (su >= 0) key[su] = 2 * p;
     }
@@ -247,6 +265,7 @@ __global__ __launch_bounds__(256) void pair_grad16_kernel(const StepArgs a) {
             const int iv = __shfl(myv, j, 16), iu = __shfl(myu, j, 16);
             const int slv = __shfl(my_sv, j, 16), slu = __shfl(my_su, j, 16);
             const bool st = STAGED && slv >= 0;
+            unsigned long long *hv = STAGED && !st ? hub_row(a.hub, slv, a.ld) : nullptr;
             float *gv = st ? a.stage + (int64_t)slv * a.ld : a.gE + (int64_t)iv * a.ld;
 #pragma unroll
             for (int i = 0; i < NF; ++i) {
@@ -255,6 +274,7 @@ __global__ __launch_bounds__(256) void pair_grad16_kernel(const StepArgs a) {
                     accu[i] += ds * V[r][i] + a.lambda * U[r][i];
                     const float gval = ds * U[r][i] + a.lambda * V[r][i];
                     if (st) gv[f] = gval;
+                    else if (STAGED && hv) hub_add(hv + f, gval, a.hub.scale);
                     else atomicAdd(gv + f, gval);
                 }
             }
@@ -263,7 +283,8 @@ __global__ __launch_bounds__(256) void pair_grad16_kernel(const StepArgs a) {
                 if (st) {
                     a.stage_b[slv] = gbv;
                 } else {
-                    atomicAdd(a.gb + iv, gbv);
+                    if (STAGED && hv) hub_add(hv + a.ld, gbv, a.hub.scale);
+                    else atomicAdd(a.gb + iv, gbv);
                     if (a.track) a.touched[iv] = 1;
                 }
             }
@@ -278,10 +299,14 @@ __global__ __launch_bounds__(256) void pair_grad16_kernel(const StepArgs a) {
                     if (t == 0) a.stage_b[slu] = 0.f;
                 } else {
                     float *gu = a.gE + (int64_t)iu * a.ld;
+                    unsigned long long *hu = STAGED ? hub_row(a.hub, slu, a.ld) : nullptr;
 #pragma unroll
                     for (int i = 0; i < NF; ++i) {
                         const int f = t + 16 * i;
-                        if (f < a.ld) atomicAdd(gu + f, accu[i]);
+                        if (f < a.ld) {
+                            if (STAGED && hu) hub_add(hu + f, accu[i], a.hub.scale);
+                            else atomicAdd(gu + f, accu[i]);
+                        }
                     }
                     if (t == 0 && a.track) a.touched[iu] = 1;
                 }
@@ -312,6 +337,7 @@ struct PathArgs {
     // stores), or -1 = the node's table row collects too many gradients for one reducing group -> atomics as before
     const int32_t *slot;
     float *stage, *stage_b;
+    HubAcc hub;
 };
 
 // Staged generator gradient (single replica, lazy Adam / SGD).  The gradient rows of a G pass used to be ADDED to the
@@ -322,7 +348,8 @@ struct PathArgs {
 // accumulator round trip.  The slot inside a segment is the rank the counting atomic returned, i.e. arrival order, which
 // differs from run to run; the sum does not: every stage row carries the path position it came from (sg_key) and the
 // reducing group adds its segment in ascending key order -- a deterministic sum for those rows.  Hub rows (> T gradients)
-// keep the atomic path (run-dependent fp32 order) and the flag -> list -> sparse_opt_kernel update.
+// add 64-bit fixed-point sums (HubAcc: order independent), hub_finalize_kernel moves them into the fp32 accumulators, and
+// the flag -> list -> sparse_opt_kernel update applies them.
 // `flag` (early launches behind the walk, enqueue_path_slots): the walk launch's status word; 2 = the launch is being rerun, its
 // paths are not final -> count nothing (the rerun brings its own launch of these kernels)
 __global__ __launch_bounds__(256) void path_count_kernel(const int32_t *paths, const int32_t *path_len, int stride, int64_t n_walks,
@@ -343,7 +370,7 @@ __global__ __launch_bounds__(256) void path_slot_kernel(const int32_t *paths, co
     const int c = (int)(idx - w * stride), L = path_len[w] - 1;
     if (L <= 1 || c >= L) return;
     const int nd = paths[idx];
-    const int sl = cnt[nd] <= T ? off[nd] + slot[idx] : -1;
+    const int sl = cnt[nd] <= T ? off[nd] + slot[idx] : -3 - off[nd];
     slot[idx] = sl;
     if (sl >= 0) key[sl] = (int32_t)idx;  // n_pos < 2^31 (run_path_step)
 }
@@ -445,13 +472,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NF <= 8 ? 3
             return;
         }
         float *g = a.gE + (int64_t)nd * a.ld;
+        unsigned long long *h = STAGED ? hub_row(a.hub, sslot[sl], a.ld) : nullptr;
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
             const int f = t + 16 * i;
-            if (f < a.ld) atomicAdd(g + f, A[sl][i]);
+            if (f < a.ld) {
+                if (STAGED && h) hub_add(h + f, A[sl][i], a.hub.scale);
+                else atomicAdd(g + f, A[sl][i]);
+            }
         }
         if (t == 0) {
-            if (gb[sl] != 0.f) atomicAdd(a.gb + nd, gb[sl]);
+            if (STAGED && h) {
+                if (gb[sl] != 0.f) hub_add(h + a.ld, gb[sl], a.hub.scale);
+            } else if (gb[sl] != 0.f) {
+                atomicAdd(a.gb + nd, gb[sl]);
+            }
             if (a.track) a.touched[nd] = 1;
         }
     };
@@ -1251,12 +1286,66 @@ static int64_t stage_bytes_cap() {
     return cap;
 }
 
+// Hub rows of a staging index (count > T: no stage segment): numbered in the row's `off` entry, which the segments leave
+// unused there, listed in `rows`, counted in *nhub (the index's totals[2]).  The numbering is arrival order; the sums are not.
+__global__ __launch_bounds__(256) void hub_index_kernel(const int32_t *cnt, int64_t n, int T, int32_t *off, int32_t *rows, int64_t *nhub) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || cnt[i] <= T) return;
+    const int h = (int)atomicAdd((unsigned long long *)nhub, 1ull);
+    off[i] = h;
+    rows[h] = (int32_t)i;
+}
+
+// ... and their fixed-point sums into the fp32 accumulators (zero for these rows: hubs receive nothing else), clearing the sums
+__global__ __launch_bounds__(256) void hub_finalize_kernel(unsigned long long *acc, const int32_t *rows, const int64_t *nhub, int64_t cap, int ld,
+                                                           double inv_scale, float *gE, float *gb) {
+    const int64_t n = min(*nhub, cap) * (ld + 1);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long v = acc[i];
+        if (!v) continue;
+        acc[i] = 0ull;
+        const int64_t h = i / (ld + 1);
+        const int f = (int)(i - h * (ld + 1));
+        const float x = (float)((double)(long long)v * inv_scale);
+        if (f < ld) gE[(int64_t)rows[h] * ld + f] += x;
+        else gb[rows[h]] += x;
+    }
+}
+
+// fixed-point units per gradient unit: 2^32, times 2^floor(log2 n) where the pass scales its gradients by 1 / n (G)
+static float hub_scale(bool per_pair_mean, int64_t n) {
+    return std::ldexp(1.0f, 32 + (per_pair_mean && n > 1 ? (int)std::ilogb((double)n) : 0));
+}
+
+static HubAcc hub_args(gg_ctx *ctx, float scale) {
+    return HubAcc{ctx->hub_acc.as<unsigned long long>(), ctx->hub_cap, scale};
+}
+
+// number the hubs of the index just built on `stream` (its totals word 2 counts them)
+static int hub_index(gg_ctx *ctx, const int32_t *cnt, int32_t *off, DevBuf &rows, int64_t *tot, hipStream_t stream) {
+    GG_HIP(ctx, rows.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
+    GG_HIP(ctx, hipMemsetAsync(tot + 2, 0, sizeof(int64_t), stream));
+    hipLaunchKernelGGL(hub_index_kernel, dim3((unsigned)cdiv(ctx->n_node, 256)), dim3(256), 0, stream, cnt, (int64_t)ctx->n_node, ctx->sg_threshold, off,
+                       rows.as<int32_t>(), tot + 2);
+    GG_HIP(ctx, hipGetLastError());
+    return GG_OK;
+}
+
+static void hub_finalize(gg_ctx *ctx, bool early_index, float scale, float *gE, float *gb) {
+    DevBuf &rows = early_index ? ctx->sgp_hub : ctx->sg_hub, &tot = early_index ? ctx->sgp_tot : ctx->sg_tot;
+    const int64_t n = ctx->hub_cap * (ctx->ld + 1);
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 2048));
+    hipLaunchKernelGGL(hub_finalize_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->hub_acc.as<unsigned long long>(), rows.as<int32_t>(),
+                       tot.as<int64_t>() + 2, ctx->hub_cap, ctx->ld, 1.0 / (double)scale, gE, gb);
+}
+
 static int staged_reserve(gg_ctx *ctx, int64_t n_occ, int64_t n_stage) {
     if (n_stage * (int64_t)(ctx->ld + 2) * 4 > stage_bytes_cap()) return 1;
     const size_t cnt_before = ctx->sg_cnt.bytes;
     GG_HIP(ctx, ctx->sg_cnt.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
     // the counts are zero between passes -- every update resets the rows it applies -- unless the buffer is new or an earlier
     // staged pass failed half way (sg_cnt_dirty stays set): then they are cleared here, stale counts would mis-place stage rows
+    const bool was_dirty = ctx->sg_cnt_dirty;  // (a pass that failed half way may also have left hub sums behind)
     if (ctx->sg_cnt.bytes != cnt_before || ctx->sg_cnt_dirty) GG_HIP(ctx, hipMemsetAsync(ctx->sg_cnt.p, 0, ctx->sg_cnt.bytes, ctx->stream));
     ctx->sg_cnt_dirty = true;
     GG_HIP(ctx, ctx->sg_off.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
@@ -1265,6 +1354,17 @@ static int staged_reserve(gg_ctx *ctx, int64_t n_occ, int64_t n_stage) {
     GG_HIP(ctx, ctx->sg_bias.reserve(sizeof(float) * (size_t)n_stage));
     GG_HIP(ctx, ctx->sg_key.reserve(sizeof(int32_t) * (size_t)n_stage));
     GG_HIP(ctx, ctx->sg_tot.reserve(sizeof(int64_t) * 4));
+    {  // a hub has more than T of the n_occ gradients; the sums stay zero between passes (hub_finalize_kernel clears them)
+        const int64_t cap = std::min<int64_t>(ctx->n_node, n_occ / ((int64_t)ctx->sg_threshold + 1) + 1);
+        const size_t before = ctx->hub_acc.bytes;
+        if (ctx->hub_acc.reserve(sizeof(unsigned long long) * (size_t)cap * (ctx->ld + 1)) != hipSuccess) {
+            (void)hipGetLastError();  // out of memory for the hub sums: like the stage below, the atomic kernels need none
+            ctx->hub_cap = 0;
+            return 1;
+        }
+        if (ctx->hub_acc.bytes != before || was_dirty) GG_HIP(ctx, hipMemsetAsync(ctx->hub_acc.p, 0, ctx->hub_acc.bytes, ctx->stream));
+        ctx->hub_cap = (int64_t)(ctx->hub_acc.bytes / (sizeof(unsigned long long) * (ctx->ld + 1)));
+    }
     if (ctx->sg_rows.reserve(sizeof(float) * (size_t)n_stage * ctx->ld) != hipSuccess) {
         (void)hipGetLastError();  // out of memory for the stage: not an error, the atomic kernels need no stage
         return 1;
@@ -1392,14 +1492,19 @@ int run_step(gg_ctx *ctx, int which, const int32_t *d_u, const int32_t *d_v, con
         hipLaunchKernelGGL(pair_occ_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_u, d_v, n, s.ppg, cnt, slot_v, slot_u);
         rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sg_list.as<int4>(), ctx->sg_tot.as<int64_t>());
         if (rc != GG_OK) return rc;
+        rc = hub_index(ctx, cnt, off, ctx->sg_hub, ctx->sg_tot.as<int64_t>(), ctx->stream);
+        if (rc != GG_OK) return rc;
         hipLaunchKernelGGL(pair_occ_slot_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_u, d_v, n, cnt, off, ctx->sg_threshold, slot_v, slot_u,
                            ctx->sg_key.as<int32_t>());
         s.slot_v = slot_v; s.slot_u = slot_u;
         s.stage = ctx->sg_rows.as<float>(); s.stage_b = ctx->sg_bias.as<float>();
+        const float scale = hub_scale(!s.is_d, n);
+        s.hub = hub_args(ctx, scale);
         // (staged implies ppg = 16 and ld <= 256)
         if (nf <= 4) hipLaunchKernelGGL((pair_grad16_kernel<4, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
         else if (nf <= 8) hipLaunchKernelGGL((pair_grad16_kernel<8, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
         else hipLaunchKernelGGL((pair_grad16_kernel<16, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
+        hub_finalize(ctx, false, scale, s.gE, s.gb);
         if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | optimizer
         return staged_finish(ctx, which, n, 2 * (int64_t)n);
     }
@@ -1486,13 +1591,18 @@ int run_path_step(gg_ctx *ctx) {
         hipLaunchKernelGGL(path_count_kernel, pgrid, dim3(256), 0, ctx->stream, p.paths, p.path_len, p.stride, p.n_walks, cnt, slot, (const unsigned long long *)nullptr);
         rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sg_list.as<int4>(), ctx->sg_tot.as<int64_t>());
         if (rc != GG_OK) return rc;
+        rc = hub_index(ctx, cnt, off, ctx->sg_hub, ctx->sg_tot.as<int64_t>(), ctx->stream);
+        if (rc != GG_OK) return rc;
         hipLaunchKernelGGL(path_slot_kernel, pgrid, dim3(256), 0, ctx->stream, p.paths, p.path_len, p.stride, p.n_walks, cnt, off, ctx->sg_threshold, slot,
                            ctx->sg_key.as<int32_t>(), (const unsigned long long *)nullptr);
     }
     p.slot = slot;
     p.stage = ctx->sg_rows.as<float>();
     p.stage_b = ctx->sg_bias.as<float>();
+    const float scale = hub_scale(true, n);
+    p.hub = hub_args(ctx, scale);
     launch_path_grad<true>(ctx, p, blocks, nf);
+    hub_finalize(ctx, early, scale, p.gE, p.gb);
     if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | optimizer
     return staged_finish(ctx, 0, n, n_pos, early);
 }
@@ -1508,7 +1618,7 @@ int enqueue_path_slots(gg_ctx *ctx) {
     if (!staged_allowed(ctx) || ctx->cfg.window_size > 2 || n_walks == 0 || n_pos >= (1ll << 31)) return GG_OK;
     if (ctx->g_slots_unused >= 2) {  // the caller runs minibatch steps (run_step): the index would be built and dropped per prepare_g
         if (ctx->sgp_slot.p) {       // (hipFree waits for the device: once, when the schedule is recognised)
-            for (DevBuf *b : {&ctx->sgp_cnt, &ctx->sgp_off, &ctx->sgp_slot, &ctx->sgp_list, &ctx->sgp_key, &ctx->sgp_scan}) b->release();
+            for (DevBuf *b : {&ctx->sgp_cnt, &ctx->sgp_off, &ctx->sgp_slot, &ctx->sgp_list, &ctx->sgp_key, &ctx->sgp_scan, &ctx->sgp_hub}) b->release();
             ctx->sgp_cnt_clean = false;
         }
         return GG_OK;
@@ -1529,6 +1639,8 @@ int enqueue_path_slots(gg_ctx *ctx) {
     int32_t *cnt = ctx->sgp_cnt.as<int32_t>(), *off = ctx->sgp_off.as<int32_t>(), *slot = ctx->sgp_slot.as<int32_t>();
     hipLaunchKernelGGL(path_count_kernel, pgrid, dim3(256), 0, st, ctx->w_paths.as<int32_t>(), ctx->w_len.as<int32_t>(), ctx->w_stride, n_walks, cnt, slot, flag);
     int rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sgp_list.as<int4>(), ctx->sgp_tot.as<int64_t>(), st, &ctx->sgp_scan);
+    if (rc != GG_OK) return rc;
+    rc = hub_index(ctx, cnt, off, ctx->sgp_hub, ctx->sgp_tot.as<int64_t>(), st);
     if (rc != GG_OK) return rc;
     hipLaunchKernelGGL(path_slot_kernel, pgrid, dim3(256), 0, st, ctx->w_paths.as<int32_t>(), ctx->w_len.as<int32_t>(), ctx->w_stride, n_walks, cnt, off,
                        ctx->sg_threshold, slot, ctx->sgp_key.as<int32_t>(), flag);

@@ -4,9 +4,9 @@
     python profiles/summarize.py <round-tag> <kernel_trace_dir> <fetch_dir> <write_dir> [<l2_dir> [<sq_dir> [<timeline_dir>]]]
 
 Commands that produced the inputs (on the MI355X box, `cd /tmp && export TMPDIR=/tmp` first):
-    rocprofv3 --kernel-trace --stats --output-format csv -d <kernel_trace_dir> -o b -- python bench.py --no-cpu-baseline
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d <fetch_dir> -o f -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d <write_dir> -o w -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --stats --output-format csv -d <kernel_trace_dir> -o b -- python bench.py --full --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d <fetch_dir> -o f -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d <write_dir> -o w -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 PMC passes are separate runs (FETCH_SIZE and WRITE_SIZE do not fit one pass).  gfx950 correction
 (MI355X_MICROARCH.md, HBM section): FETCH_SIZE counts 64 B per 128 B request of wide coalesced reads,
 so read bytes = 2 * FETCH_SIZE KiB; WRITE_SIZE is taken as reported.

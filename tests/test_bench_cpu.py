@@ -78,3 +78,82 @@ def test_comm_model_prices_the_exchange_on_xgmi():
         assert 0.0 < t32["weak_scaling_efficiency_estimate"] < t16["weak_scaling_efficiency_estimate"] < 1.0
     assert m["P=8"]["modelled_time_owner_fp32"]["weak_scaling_efficiency_estimate"] < 0.8     # not near-linear at this batch: said so in DESIGN section 7
     assert m["assumptions"]["xgmi_link_GBs"] == 153.0
+
+
+def test_dump_outputs_writes_fixed_samples_of_the_last_step(tmp_path, monkeypatch):
+    """`--dump-outputs DIR` (off by default, like `--full`): both models' table rows and biases, the D rows and the G pairs
+    of the last step as float32 / float64 .npy files -- the same seeded sample on every run, under 64 MB in all.  The
+    engine is a stand-in with the Engine's getters (no GPU in this container)."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+
+    n, d = 50_000, 128
+    rs = np.random.RandomState(3)
+
+    class Eng:
+        n_node, n_emb = n, d
+        emb = [rs.rand(n, d).astype(np.float32) for _ in range(2)]
+        d_data = (rs.randint(0, n, 300_000).astype(np.int32), rs.randint(0, n, 300_000).astype(np.int32), (rs.rand(300_000) < 0.5).astype(np.float32))
+        g_data = (rs.randint(0, n, 1000).astype(np.int32), rs.randint(0, n, 1000).astype(np.int32), rs.rand(1000).astype(np.float32))
+
+        def get_embeddings(self, which):
+            return self.emb[which].copy()
+
+        def get_bias(self, which):
+            return np.arange(self.n_node, dtype=np.float32) + 0.5 * which
+
+        def get_d_data(self):
+            return self.d_data
+
+        def get_g_data(self):
+            return self.g_data
+
+    eng = Eng()
+    bench.dump_outputs(eng, str(tmp_path / "a"))
+    bench.dump_outputs(eng, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".npy" for k in ("gen_emb_rows", "gen_bias_rows", "dis_emb_rows", "dis_bias_rows", "d_center", "d_neighbor",
+                                                "d_label", "g_node_1", "g_node_2", "g_reward"))
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n, v in out.items():
+        assert v.dtype in (np.float32, np.float64), n
+        assert np.array_equal(v, np.load(tmp_path / "b" / (n + ".npy"))), n   # the same sample on every run
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    rows = out["gen_bias_rows"].astype(np.int64)   # the bias of node i is i here: the sampled node ids
+    assert len(rows) == bench.DUMP_TABLE_BYTES // (4 * Eng.n_emb) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(out["gen_emb_rows"], Eng.emb[0][rows]) and np.array_equal(out["dis_emb_rows"], Eng.emb[1][rows])
+    assert np.array_equal(out["dis_bias_rows"], rows + 0.5)
+    assert len(out["d_center"]) == bench.DUMP_PAIRS and set(out["d_label"]) <= {0.0, 1.0}
+    assert np.array_equal(out["g_node_1"], Eng.g_data[0]) and np.array_equal(out["g_reward"], Eng.g_data[2])   # below the cap: all pairs
+
+
+def test_full_and_dump_outputs_combine_with_the_legs_flags(tmp_path, monkeypatch):
+    """--full / --dump-outputs parse together with the flags of the legs they gate; a narrow table keeps the dump small."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out", "--no-cpu-baseline", "--no-strict", "--fresh-batches", "1",
+                                      "--overlap-steps", "2", "--continuity-roots", "512", "--steps", "7"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and a.no_cpu_baseline and a.no_strict and a.fresh_batches == 1 and a.overlap_steps == 2
+    assert a.continuity_roots == 512 and a.steps == 7
+
+    class Narrow:  # d = 1 and many nodes: the row sample is capped, not only by bytes per table
+        n_node, n_emb = 5_000_000, 1
+
+        def get_embeddings(self, which):
+            return np.zeros((self.n_node, 1), np.float32)
+
+        def get_bias(self, which):
+            return np.zeros(self.n_node, np.float32)
+
+        def get_d_data(self):
+            return np.zeros(10, np.int32), np.zeros(10, np.int32), np.zeros(10, np.float32)
+
+        def get_g_data(self):
+            return np.zeros(10, np.int32), np.zeros(10, np.int32), np.zeros(10, np.float32)
+    bench.dump_outputs(Narrow(), str(tmp_path))
+    sizes = {n: os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)}
+    assert sum(sizes.values()) < 64 << 20 and np.load(tmp_path / "gen_bias_rows.npy").shape == (bench.DUMP_TABLE_ROWS,)

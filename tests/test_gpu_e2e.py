@@ -418,3 +418,36 @@ def test_bench_gpus_2_self_launches_two_ranks():
     h2 = lines[2]["value"] * lines[2]["ms_per_step"]
     assert 1.6 < h2 / h1 < 2.4
     assert 1.6 < lines[2]["g_pairs_per_step_all_ranks"] / lines[1]["g_pairs_per_step_all_ranks"] < 2.4
+
+
+def test_bench_plain_runs_repeat_bit_for_bit_and_full_adds_the_legs(tmp_path):
+    """Two plain `bench.py --dump-outputs` runs with the same arguments write the same arrays, bit for bit: the fused passes
+    take the staged path (>= 16 384 pairs per pass, one replica) and the power-law graph has hub rows (> GG_STAGE_T = 64
+    gradients), whose sums are order independent.  The plain line carries none of the legs behind the timed region; --full
+    adds them (CPU baselines and strict mode skipped here for time)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--nodes", "50000", "--roots", "2048", "--steps", "3", "--warmup", "2", "--continuity-roots", "512"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GG_STAGE_T", "GG_NO_STAGED_GRAD")}
+
+    def run(extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + extra, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    moved = ("batch_of_rounds_1_2", "end_to_end_with_tree_build", "strict_mode", "cpu_baseline")
+    lines = [run(["--dump-outputs", str(tmp_path / k)]) for k in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert not any(k in line for k in moved) and line["roofline"]["solo"] is None
+        assert line["d_pairs_per_step_all_ranks"] >= 16384 and line["g_pairs_per_step_all_ranks"] >= 16384  # staged passes
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert len(names) == 10 and names == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.size > 0, n
+        assert np.array_equal(x, y), n
+    full = run(["--full", "--no-cpu-baseline", "--no-strict", "--fresh-batches", "1", "--overlap-steps", "2"])
+    assert "batch_of_rounds_1_2" in full and "end_to_end_with_tree_build" in full and full["roofline"]["solo"] is not None

@@ -390,6 +390,26 @@ def test_staged_generator_gradient_equals_the_atomic_path(ga, opt, threshold, mo
 
 
 @pytest.mark.parametrize("opt", ["lazy", "sgd"])
+def test_staged_hub_rows_are_bit_reproducible(ga, opt, monkeypatch):
+    """Hub rows of a staged pass (more gradients than GG_STAGE_T: threshold 3 makes most rows of this graph hubs) add their
+    gradients as 64-bit fixed-point integers, whose sum does not depend on the order the atomics arrive in: four engines
+    repeat the staged G pass bit for bit (test_staged_generator_gradient_equals_the_atomic_path checks the values)."""
+    optimizer = ga.GG_OPT_ADAM_LAZY if opt == "lazy" else ga.GG_OPT_SGD
+    monkeypatch.setenv("GG_STAGE_T", "3")
+    tabs = []
+    for _ in range(4):
+        _, n, _, _, _, _, e = _setup_graph_engine(ga, optimizer=optimizer)
+        slots = np.arange(n, dtype=np.int32)
+        for rnd in range(2):
+            e.prepare_g(slots, 20, 4, 2 * rnd + 1, fetch=False)
+            e.g_pass([0], 1 << 30)
+        tabs.append((e.get_embeddings(0).view(np.uint32), e.get_bias(0).view(np.uint32)))
+        e.close()
+    for k in range(1, 4):
+        assert np.array_equal(tabs[0][0], tabs[k][0]) and np.array_equal(tabs[0][1], tabs[k][1])
+
+
+@pytest.mark.parametrize("opt", ["lazy", "sgd"])
 def test_staged_sums_are_bit_reproducible(ga, opt):
     """Fused D pass (>= 16 384 pairs) on a table large enough that no row collects more than the default 64 gradients:
     every row is staged and summed in source order -- segments of 1 .. 64 rows, i.e. one to four keys per lane in the
