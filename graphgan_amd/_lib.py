@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgraphgan_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "graphgan_hip.h")
-ABI_VERSION = 7  # == GG_ABI_VERSION of include/graphgan_hip.h (tests/test_host_cpu.py keeps header, binding and library in step)
+ABI_VERSION = 8  # == GG_ABI_VERSION of include/graphgan_hip.h (tests/test_host_cpu.py keeps header, binding and library in step)
 
 
 def header_abi_version(path=HEADER_PATH):
@@ -112,6 +112,7 @@ SIGNATURES = {
     "gg_g_step": (ctypes.c_int, [_P, _P, _P, _P, _i32]),
     "gg_all_score": (ctypes.c_int, [_P, _P, _i32, _P]),
     "gg_all_score_reduce": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]),
+    "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

@@ -59,3 +59,5 @@ engine_tree_budget_gb = 160.0  # all N BFS trees stay resident (reference :31-46
 engine_batch_roots = 0        # roots per batch of a root-batched epoch; 0 = what the budget holds (at most 16 384)
 engine_emb_text = True        # write the reference's .emb text after every epoch (graph_gan.py:293-306); ~50 GB per write at N = 10^7, d = 256
 engine_emb_sidecar = False    # also write <emb_filename>.bin: the same fp32 numbers in binary (utils.read_embeddings_bin)
+engine_rec_ks = (2, 10, 20)   # app = "recommendation": the K of the P@K / R@K results line (each in [1, 256])
+engine_rec_precision = "fp32"  # app = "recommendation": ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)

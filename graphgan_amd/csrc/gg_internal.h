@@ -290,6 +290,10 @@ struct gg_ctx {
     int64_t owner_min_bound = 4096;   // GG_COMM_OWNER_MIN: steps of fewer pairs never try it (its two host round trips outweigh a minibatch)
     int64_t comm_steps_owner = 0;     // optimizer steps that took it (gg_comm_stats counts them with the sparse steps)
 
+    // gg_topk_scores with exclude = 1 (topk_score.hip): the resident adjacency with every list sorted; dropped by gg_set_graph_csr
+    gg::DevBuf topk_adj;
+    bool topk_adj_valid = false;
+
     std::string err;
 };
 

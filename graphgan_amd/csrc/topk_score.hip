@@ -1,0 +1,454 @@
+// topk_score.hip -- streamed top-K node retrieval: for each requested node u the k best columns of S[u, :] = E[u] . E^T
+// (no bias: the evaluator's score, link_prediction.py:26-27), optionally without u itself and u's neighbours in the resident
+// training graph.  The rows of S are produced tile by tile on the matrix cores exactly as K7 (all_score.hip) produces them and
+// consumed in registers; nothing of size n_rows x N exists at any time.
+//
+// Order of a result row: score descending, column ascending.  Both are packed into ONE 64-bit key,
+//     key = ord(score) << 32 | ~col        (ord: the monotone unsigned image of an fp32; -0 counts as +0)
+// so "better" is "larger key", every key is distinct (columns are), and 0 is below every real key: an empty list slot.
+//
+// Work split: grid = (column splits, 32-row tiles); a workgroup's 4 wavefronts take 32 columns each of every 128-column tile
+// of its split.  Every WAVEFRONT keeps, for each of the tile's 32 rows, a private sorted K-list (in the partial buffer in
+// global memory -- it is touched only when it changes) and the list's K-th score tau in registers.  Per tile and lane the
+// 16 scores it holds are compared with their rows' tau and OR-ed into one flag; one ballot per tile decides, uniformly for the
+// wavefront, whether anything can enter a list.  After the first few tiles tau is high and nearly every tile costs those
+// 16 compares; the rare tiles with candidates take the insertion path: per (row, half-wave) the candidates are checked for
+// eligibility (exclude: a binary search in the sorted adjacency of the row's node -- only scores >= tau ever get there, and an
+// excluded column never enters a list, so it cannot raise tau), ranked among themselves and against the list, and merged
+// in place; the new K-th key becomes the row's tau.  A wavefront's columns only grow, so a candidate never ties a list entry.
+// topk_merge_kernel then merges the (split, wavefront) lists of a row on the device (one workgroup per row, rank merge in LDS,
+// a list whose head does not beat the running K-th key is skipped).
+//   fp32: v_mfma_f32_32x32x2_f32 with the tile staging of all_score_reduce_f32_kernel -- the same k-ordered fmaf chain from
+//         0.0, so the scores are bit-identical to gg_all_score (zero bias) and the oracle's rows;
+//   bf16: v_mfma_f32_32x32x16_bf16 on a bf16 copy of the table (round to nearest even, K7's tiled layout), fp32 accumulate;
+//         the requested rows' fragments stay in registers, every lane streams its own column's k-slices.
+#include <math.h>
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "gg_internal.h"
+
+namespace gg {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned long long u64;
+
+constexpr int TK_KC = 32;          // k-chunk of the fp32 tile staging (as K7)
+constexpr int TK_CHUNK = 4096;     // requested rows per internal pass
+constexpr int TK_MAX_K = 256;
+constexpr size_t TK_PART_CAP = size_t(256) << 20;  // bytes of partial lists per pass, at most
+
+struct TopkOut {
+    const int32_t *rows;      // [n_rows] node ids of the pass
+    int n_rows, k;
+    const int64_t *adj_ptr;   // exclusion: the graph's row offsets and its column lists sorted per node (NULL: exclude = 0)
+    const int32_t *adj;
+    u64 *part;                // [n_rows][n_sub][k] keys, descending, 0 = empty
+    int n_sub;                // 4 per column split
+};
+
+__device__ __forceinline__ u64 topk_key(float x, int col) {
+    uint32_t u = __float_as_uint(x);
+    u = u == 0x80000000u ? 0u : u;
+    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((u64)o << 32) | (uint32_t)~(uint32_t)col;
+}
+
+__device__ __forceinline__ float key_score(u64 key) {
+    const uint32_t o = (uint32_t)(key >> 32);
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__device__ __forceinline__ u64 readlane64(u64 v, int j) {
+    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return ((u64)hi << 32) | lo;
+}
+
+// Merge the candidates of one row (lanes with `cand`, key `key`; all their columns lie behind every entry of the list) into
+// the wavefront's list L (k keys, descending, zeros behind the last entry).  Wavefront-wide; returns the new k-th key (0: the
+// list is not full).  Every lane reads what it needs before any lane writes (the loaded values feed the stores).
+__device__ u64 wave_insert(u64 *L, int k, bool cand, u64 key) {
+    const int lane = threadIdx.x & 63;
+    const u64 m = __builtin_amdgcn_ballot_w64(cand);
+    int pos = k;
+    if (cand) {  // entries of L above the key: a prefix
+        int lo = 0, hi = k;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (L[mid] > key) lo = mid + 1;
+            else hi = mid;
+        }
+        pos = lo;
+    }
+    u64 lv[TK_MAX_K / 64];
+    int sh[TK_MAX_K / 64];
+#pragma unroll
+    for (int q = 0; q < TK_MAX_K / 64; ++q) {
+        const int i = lane + 64 * q;
+        lv[q] = i < k ? L[i] : 0ull;
+        sh[q] = 0;
+    }
+    u64 mm = m;
+    while (mm) {  // (uniform: at most 32 candidates)
+        const int j = __builtin_ctzll(mm);
+        mm &= mm - 1;
+        const u64 kj = readlane64(key, j);
+        pos += (cand && kj > key) ? 1 : 0;
+#pragma unroll
+        for (int q = 0; q < TK_MAX_K / 64; ++q) sh[q] += kj > lv[q] ? 1 : 0;
+    }
+    u64 at_last = 0, old_last = 0;  // the key that lands at position k - 1; the one there before
+#pragma unroll
+    for (int q = 0; q < TK_MAX_K / 64; ++q) old_last = lane + 64 * q == k - 1 ? lv[q] : old_last;
+#pragma unroll
+    for (int q = 0; q < TK_MAX_K / 64; ++q) {
+        const int i = lane + 64 * q, p = i + sh[q];
+        if (i < k && lv[q] != 0 && p < k) {
+            L[p] = lv[q];
+            if (p == k - 1) at_last = lv[q];
+        }
+    }
+    if (cand && pos < k) {
+        L[pos] = key;
+        if (pos == k - 1) at_last = key;
+    }
+    __threadfence_block();  // (the next insertion into this list reads what the lanes wrote)
+    const u64 w = __builtin_amdgcn_ballot_w64(at_last != 0);
+    return w ? readlane64(at_last, __builtin_ctzll(w)) : readlane64(old_last, (k - 1) & 63);  // (nothing entered: unchanged)
+}
+
+__device__ __forceinline__ bool adj_contains(const int32_t *a, int64_t n, int col) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < col) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && a[lo] == col;
+}
+
+// Per wavefront: the k-lists of the tile's 32 rows (sub-list `sub`) and, per lane, tau of the 16 rows it holds
+// (row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), the matrix instruction's C layout).
+struct WaveLists {
+    float tau[16];
+};
+
+__device__ __forceinline__ u64 *list_of(const TopkOut &o, int row, int sub) { return o.part + ((int64_t)row * o.n_sub + sub) * o.k; }
+
+__device__ __forceinline__ void lists_init(WaveLists &st, const TopkOut &o, int r0, int sub) {
+    const int lane = threadIdx.x & 63, hi = lane >> 5;
+    for (int rr = 0; rr < 32; ++rr) {
+        if (r0 + rr >= o.n_rows) break;
+        u64 *L = list_of(o, r0 + rr, sub);
+        for (int i = lane; i < o.k; i += 64) L[i] = 0ull;
+    }
+    __threadfence_block();
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = r0 + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
+        st.tau[reg] = row < o.n_rows ? -INFINITY : INFINITY;  // (rows behind the pass never take a candidate)
+    }
+}
+
+// One finished 32 x 32 tile of the wavefront: lane holds column `col` (valid iff ok) of 16 rows.
+__device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, int r0, int sub, const f32x16 &acc, int col, bool ok) {
+    bool any = false;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) any |= acc[reg] >= st.tau[reg];
+    any &= ok;
+    if (!__builtin_amdgcn_ballot_w64(any)) return;
+    const int lane = threadIdx.x & 63, hi = lane >> 5;
+#pragma unroll 1
+    for (int reg = 0; reg < 16; ++reg) {
+        float x = acc[0], t = st.tau[0];
+#pragma unroll
+        for (int r2 = 1; r2 < 16; ++r2) {
+            x = reg == r2 ? acc[r2] : x;
+            t = reg == r2 ? st.tau[r2] : t;
+        }
+        const bool p = ok && x >= t;
+        const u64 pm = __builtin_amdgcn_ballot_w64(p);
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            if (((pm >> (32 * h)) & 0xffffffffull) == 0) continue;
+            const int row = r0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            bool cand = p && hi == h;
+            if (cand && o.adj) {
+                const int u = o.rows[row];
+                const int64_t b = o.adj_ptr[u], e = o.adj_ptr[u + 1];
+                cand = col != u && !adj_contains(o.adj + b, e - b, col);
+            }
+            const u64 kth = wave_insert(list_of(o, row, sub), o.k, cand, cand ? topk_key(x, col) : 0ull);
+            const float nt = kth ? key_score(kth) : -INFINITY;
+#pragma unroll
+            for (int r2 = 0; r2 < 16; ++r2) st.tau[r2] = (reg == r2 && hi == h) ? nt : st.tau[r2];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_f32_kernel(const float *E, int n_node, int ld, int cols_per_split, TopkOut o) {
+    extern __shared__ float As_all[];  // [32][ld + 1]: the tile's 32 requested rows, staged once
+    __shared__ float Bs[128][TK_KC + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + wv;
+    const int lda = ld + 1;
+    for (int i = tid; i < 32 * (ld / 4); i += 256) {
+        const int r = i / (ld / 4), kk = (i % (ld / 4)) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r0 + r < o.n_rows) v = *(const float4 *)(E + (int64_t)o.rows[r0 + r] * ld + kk);
+        float *d = As_all + r * lda + kk;
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+    WaveLists st;
+    lists_init(st, o, r0, sub);
+    const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
+    for (int c0 = cbeg; c0 < cend; c0 += 128) {
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int k0 = 0; k0 < ld; k0 += TK_KC) {
+            __syncthreads();  // also orders the A staging before its first use
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = (tid >> 3) + 32 * i, kk = (tid & 7) * 4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c0 + r < cend && k0 + kk < ld) v = *(const float4 *)(E + (int64_t)(c0 + r) * ld + k0 + kk);
+                Bs[r][kk] = v.x; Bs[r][kk + 1] = v.y; Bs[r][kk + 2] = v.z; Bs[r][kk + 3] = v.w;
+            }
+            __syncthreads();
+            const int kmax = min(TK_KC, ld - k0);
+            for (int kk = 0; kk < kmax; kk += 2) {
+                const float a = As_all[(lane & 31) * lda + k0 + kk + (lane >> 5)];
+                const float b = Bs[wv * 32 + (lane & 31)][kk + (lane >> 5)];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        }
+        const int col = c0 + wv * 32 + (lane & 31);
+        lists_consume(st, o, r0, sub, acc, col, col < cend);
+    }
+}
+
+// K7's tiled bf16 layout (all_score.hip, bf16_piece): the 16-byte piece {k = 16 s + 8 h .. + 8} of row r at piece index
+// ((r / 32) KS + s) 64 + 32 h + r % 32 -- the 64 lanes that load k-step s of a 32-column tile read one contiguous kilobyte.
+__device__ __forceinline__ int64_t tk_piece(int64_t r, int s, int h, int KS) { return ((r >> 5) * KS + s) * 64 + 32 * h + (r & 31); }
+
+__global__ void topk_to_bf16_kernel(const float *E, int64_t n, int64_t n_pad, int ld, int ld16, __bf16 *out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pad * ld16) return;
+    const int64_t r = i / ld16;
+    const int k = (int)(i % ld16);
+    const float v = (r < n && k < ld) ? E[r * ld + k] : 0.0f;
+    out[tk_piece(r, k >> 4, (k >> 3) & 1, ld16 / 16) * 8 + (k & 7)] = (__bf16)v;
+}
+
+// KS k-steps of 16.  The A fragments of the tile's 32 requested rows stay in registers for the whole sweep; every lane streams
+// the k-slices of its own column (B), double buffered while they fit (KS <= 16).
+template <int KS>
+__global__ __launch_bounds__(256) void topk_bf16_kernel(const uint4 *Eb, int n_node, int cols_per_split, TopkOut o) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5;
+    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + wv;
+    union Frag { uint4 u; bf16x8 v; };
+    Frag afrag[KS];
+    {
+        const int r = r0 + (lane & 31);
+        const int node = r < o.n_rows ? o.rows[r] : -1;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) afrag[s].u = node >= 0 ? Eb[tk_piece(node, s, half, KS)] : make_uint4(0u, 0u, 0u, 0u);
+    }
+    WaveLists st;
+    lists_init(st, o, r0, sub);
+    const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
+    constexpr bool PF = KS <= 16;
+    Frag bcur[KS], bnxt[PF ? KS : 1];
+    auto load_tile = [&](Frag *dst, int c0t) {  // (a prefetch behind the split's end re-reads its first tile)
+        const uint4 *brow = Eb + (int64_t)((c0t < cend ? c0t : cbeg) >> 5) * KS * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) dst[s].u = brow[64 * s];
+    };
+    if (PF) load_tile(bcur, cbeg + wv * 32);
+    for (int c0 = cbeg + wv * 32; c0 < cend; c0 += 128) {
+        const int col = c0 + (lane & 31);
+        if (PF) load_tile(bnxt, c0 + 128);
+        else load_tile(bcur, c0);
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[s].v, bcur[s].v, acc, 0, 0, 0);
+        if (PF) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) bcur[s] = bnxt[PF ? s : 0];
+        }
+        lists_consume(st, o, r0, sub, acc, col, col < cend);
+    }
+}
+
+// Count of keys > x in a descending list of k keys.
+__device__ __forceinline__ int count_above(const u64 *L, int k, u64 x) {
+    int lo = 0, hi = k;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (L[mid] > x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One workgroup per requested row: the row's n_sub lists merged into one k-list in LDS (rank merge: an entry's new position is
+// its index plus the entries of the other list above it; keys are distinct), written out as (column, score), -1 / -inf padded.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const u64 *part, int n_sub, int k, int32_t *out_col, float *out_score) {
+    __shared__ u64 cur[TK_MAX_K], nb[TK_MAX_K];
+    __shared__ u64 heads[256];
+    const int tid = threadIdx.x, row = blockIdx.x;
+    cur[tid] = 0ull;
+    const u64 *P = part + (int64_t)row * n_sub * k;
+    for (int s0 = 0; s0 < n_sub; s0 += 256) {
+        __syncthreads();
+        heads[tid] = s0 + tid < n_sub ? P[(int64_t)(s0 + tid) * k] : 0ull;
+        __syncthreads();
+        const int ns = min(256, n_sub - s0);
+        for (int j = 0; j < ns; ++j) {
+            if (heads[j] <= cur[k - 1]) continue;  // (uniform: nothing of this list beats the running k-th key; empty lists too)
+            const u64 b = tid < k ? P[(int64_t)(s0 + j) * k + tid] : 0ull;
+            nb[tid] = b;
+            __syncthreads();
+            const u64 a = tid < k ? cur[tid] : 0ull;
+            const int pa = tid + count_above(nb, k, a), pb = tid + count_above(cur, k, b);
+            __syncthreads();
+            if (a != 0 && pa < k) cur[pa] = a;
+            if (b != 0 && pb < k) cur[pb] = b;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (tid < k) {
+        const u64 key = cur[tid];
+        out_col[(int64_t)row * k + tid] = key ? (int32_t)~(uint32_t)key : -1;
+        out_score[(int64_t)row * k + tid] = key ? key_score(key) : -INFINITY;
+    }
+}
+
+}  // namespace
+
+// The resident adjacency with every node's list sorted (binary search of the exclusion test); built on first use after
+// gg_set_graph_csr, which drops it.  The resident lists themselves stay in file order (the BFS trees depend on it).
+static int ensure_sorted_adjacency(gg_ctx *ctx) {
+    if (ctx->topk_adj_valid) return GG_OK;
+    const int n = ctx->n_node;
+    std::vector<int32_t> s(ctx->h_col);
+    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([&, t]() {
+            for (int v = (int)((int64_t)n * t / nt); v < (int)((int64_t)n * (t + 1) / nt); ++v)
+                std::sort(s.begin() + ctx->h_rowptr[v], s.begin() + ctx->h_rowptr[v + 1]);
+        });
+    for (auto &x : th) x.join();
+    hipError_t e = ctx->topk_adj.reserve(sizeof(int32_t) * std::max<size_t>(s.size(), 1));
+    if (e == hipSuccess && !s.empty()) e = hipMemcpy(ctx->topk_adj.p, s.data(), sizeof(int32_t) * s.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "gg_topk_scores: sorted adjacency (%lld entries): %s", (long long)s.size(), hipGetErrorString(e));
+    ctx->topk_adj_valid = true;
+    return GG_OK;
+}
+
+}  // namespace gg
+
+using namespace gg;
+
+// gg_topk_scores: see include/graphgan_hip.h.
+extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
+                              int32_t *out_col, float *out_score, double *kernel_ms_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "gg_topk_scores: which must be 0 (generator) or 1 (discriminator)");
+    GG_CHECK(ctx, k >= 1 && k <= TK_MAX_K, GG_EINVAL, "gg_topk_scores: k = %d outside [1, %d]", k, TK_MAX_K);
+    GG_CHECK(ctx, precision == 0 || precision == 1, GG_EINVAL, "gg_topk_scores: precision must be 0 (fp32) or 1 (bf16)");
+    GG_CHECK(ctx, exclude == 0 || exclude == 1, GG_EINVAL, "gg_topk_scores: exclude must be 0 or 1");
+    GG_CHECK(ctx, out_col && out_score && (rows || n_rows >= 0) && n_rows >= 0, GG_EINVAL, "gg_topk_scores: bad argument");
+    GG_CHECK(ctx, !exclude || ctx->g_rowptr, GG_EINVAL, "gg_topk_scores: exclude = 1 needs the training graph (gg_set_graph_csr)");
+    const int n = ctx->n_node, ld = ctx->ld;
+    // bf16: k-steps of 16 elements, instantiated for 4 / 8 / 16 / 32 of them (the copy is zero padded to that)
+    const int ks_need = (ctx->n_emb + 15) / 16;
+    GG_CHECK(ctx, precision == 0 || ks_need <= 32, GG_EINVAL, "gg_topk_scores: bf16 supports n_emb <= 512 (got %d)", ctx->n_emb);
+    const size_t dyn = sizeof(float) * 32 * (size_t)(ld + 1);
+    GG_CHECK(ctx, precision == 1 || dyn <= 140 * 1024, GG_EINVAL, "gg_topk_scores: fp32 supports n_emb <= 1116 (got %d)", ctx->n_emb);
+    if (!rows) n_rows = n;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (n_rows == 0) return GG_OK;
+    if (rows)
+        for (int i = 0; i < n_rows; ++i) GG_CHECK(ctx, rows[i] >= 0 && rows[i] < n, GG_EINVAL, "gg_topk_scores: row id %d out of range", rows[i]);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    if (exclude) {
+        const int rc = ensure_sorted_adjacency(ctx);
+        if (rc != GG_OK) return rc;
+    }
+    const int KS = ks_need <= 4 ? 4 : ks_need <= 8 ? 8 : ks_need <= 16 ? 16 : 32;
+    const int ld16 = 16 * KS;
+    const int chunk = std::min(n_rows, TK_CHUNK);
+    const int row_tiles_max = cdiv(chunk, 32);
+    // enough workgroups for the chip (multiples of 128 columns per split), the partial lists of a pass within TK_PART_CAP
+    int splits = std::max(1, std::min(cdiv(n, 128), cdiv(2048, row_tiles_max)));
+    splits = std::max(1, std::min<int>(splits, (int)(TK_PART_CAP / ((size_t)chunk * 4 * k * sizeof(u64)))));
+    const int cps = cdiv(cdiv(n, splits), 128) * 128;
+    splits = cdiv(n, cps);
+    const int n_sub = 4 * splits;
+    const Model &M = ctx->model[which];
+    DevBuf d_rows, d_part, d_col, d_score, d_bf;
+    auto rel = [&]() { d_rows.release(); d_part.release(); d_col.release(); d_score.release(); d_bf.release(); };
+    hipError_t e = d_rows.reserve(sizeof(int32_t) * chunk);
+    if (e == hipSuccess) e = d_part.reserve(sizeof(u64) * (size_t)chunk * n_sub * k);
+    if (e == hipSuccess) e = d_col.reserve(sizeof(int32_t) * (size_t)chunk * k);
+    if (e == hipSuccess) e = d_score.reserve(sizeof(float) * (size_t)chunk * k);
+    const int64_t n_pad = ((int64_t)n + 31) / 32 * 32;  // the bf16 copy is tiled by 32 rows
+    if (e == hipSuccess && precision == 1) e = d_bf.reserve(sizeof(uint16_t) * (size_t)n_pad * ld16);
+    if (e != hipSuccess) { rel(); return fail(ctx, GG_ENOMEM, "gg_topk_scores: %s", hipGetErrorString(e)); }
+    if (precision == 1) {
+        const int64_t tot = n_pad * ld16;
+        hipLaunchKernelGGL(topk_to_bf16_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, M.E, (int64_t)n, n_pad, ld, ld16,
+                           (__bf16 *)d_bf.p);
+    } else if (dyn > 48 * 1024) {
+        (void)hipFuncSetAttribute((const void *)topk_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    }
+    std::vector<int32_t> ids;
+    double ms_total = 0.0;
+    for (int c0 = 0; c0 < n_rows && e == hipSuccess; c0 += chunk) {
+        const int cr = std::min(chunk, n_rows - c0);
+        const int32_t *src = rows ? rows + c0 : nullptr;
+        if (!rows) {
+            ids.resize(cr);
+            for (int i = 0; i < cr; ++i) ids[i] = c0 + i;
+            src = ids.data();
+        }
+        e = hipMemcpyAsync(d_rows.p, src, sizeof(int32_t) * cr, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) break;
+        TopkOut o{d_rows.as<int32_t>(), cr, k, exclude ? ctx->g_rowptr : nullptr, exclude ? ctx->topk_adj.as<int32_t>() : nullptr, d_part.as<u64>(), n_sub};
+        const dim3 grid(splits, cdiv(cr, 32));
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        if (precision == 0) {
+            hipLaunchKernelGGL(topk_f32_kernel, grid, dim3(256), dyn, ctx->stream, M.E, n, ld, cps, o);
+        } else {
+            const uint4 *Eb = (const uint4 *)d_bf.p;
+            if (KS == 4) hipLaunchKernelGGL(topk_bf16_kernel<4>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            else if (KS == 8) hipLaunchKernelGGL(topk_bf16_kernel<8>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            else if (KS == 16) hipLaunchKernelGGL(topk_bf16_kernel<16>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            else hipLaunchKernelGGL(topk_bf16_kernel<32>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+        }
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(cr), dim3(256), 0, ctx->stream, (const u64 *)d_part.p, n_sub, k, d_col.as<int32_t>(), d_score.as<float>());
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out_col + (int64_t)c0 * k, d_col.p, sizeof(int32_t) * (size_t)cr * k, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out_score + (int64_t)c0 * k, d_score.p, sizeof(float) * (size_t)cr * k, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        float ms = 0.f;
+        if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+        ms_total += ms;
+    }
+    rel();
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_topk_scores: %s", hipGetErrorString(e));
+    if (kernel_ms_out) *kernel_ms_out = ms_total;
+    return GG_OK;
+}

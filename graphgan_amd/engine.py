@@ -428,6 +428,28 @@ class Engine:
                                          _ptr(mx), _ptr(am), _ptr(lse), ctypes.byref(ms)))
         return dict(max=mx, argmax=am, logsumexp=lse, kernel_ms=ms.value)
 
+    def topk(self, rows=None, k=10, which=0, precision="fp32", exclude=False):
+        """Streamed top-K retrieval (gg_topk_scores): for each node of ``rows`` (None: every node) the ``k`` best columns of
+        E[u] . E^T (no bias) of model ``which`` (0 = gen, 1 = dis), ordered by score descending, column ascending; with
+        ``exclude`` without u itself and u's neighbours in the resident training graph.  Rows with fewer than ``k`` eligible
+        columns are padded with -1 / -inf.  precision "fp32" (exact) or "bf16" (bf16 inputs, fp32 accumulate).  Nothing of
+        size rows x N is materialised.  Returns dict(col int32 [n_rows, k], score fp32 [n_rows, k], kernel_ms)."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("topk: precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        if which not in (0, 1):
+            raise ValueError("topk: which must be 0 (generator) or 1 (discriminator), got %r" % (which,))
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 256:
+            raise ValueError("topk: k must be an integer in [1, 256], got %r" % (k,))
+        k = int(k)
+        rows_a = None if rows is None else _i32(rows).reshape(-1)
+        n_rows = self.n_node if rows_a is None else len(rows_a)
+        col = np.empty((n_rows, k), dtype=np.int32)
+        score = np.empty((n_rows, k), dtype=np.float32)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_topk_scores(self._ctx, which, _ptr(rows_a), n_rows, k, {"fp32": 0, "bf16": 1}[precision], int(bool(exclude)),
+                                    _ptr(col), _ptr(score), ctypes.byref(ms)))
+        return dict(col=col, score=score, kernel_ms=ms.value)
+
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""
         out = np.zeros((self.n_node, self.n_emb), dtype=np.float32)

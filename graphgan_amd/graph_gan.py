@@ -43,6 +43,7 @@ except ImportError:
 
 from graphgan_amd import _lib, engine as _engine, parallel, utils  # noqa: E402
 from graphgan_amd.evaluation import link_prediction as lp  # noqa: E402
+from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -419,6 +420,14 @@ class GraphGAN(object):
                                          engine=self.engine, which=i)
                 result = lpe.eval_link_prediction()
                 results.append(cfg.modes[i] + ":" + str(result) + "\n")
+        elif cfg.app == "recommendation":
+            # P@K / R@K of a streamed top-K on the device (gg_topk_scores, exclude = the training graph); one line per mode:
+            # "gen:P@2=<p> R@2=<r> P@10=... R@10=... P@20=... R@20=..." (no test-negatives file is read)
+            ks = tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20)))
+            for i in range(2):
+                re_ = rec.RecommendEval(cfg.emb_filenames[i], cfg.train_filename, cfg.test_filename, self.n_node, cfg.n_emb,
+                                        engine=self.engine, which=i, ks=ks, precision=_cfg(cfg, "engine_rec_precision", "fp32"))
+                results.append(rec.format_results(cfg.modes[i], re_.eval_recommendation(), ks))
         os.makedirs(os.path.dirname(cfg.result_filename) or ".", exist_ok=True)
         with open(cfg.result_filename, mode="a+") as f:
             f.writelines(results)

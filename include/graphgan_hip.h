@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GG_ABI_VERSION 7  /* round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
+#define GG_ABI_VERSION 8  /* gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
 
 enum {
     GG_OK = 0,
@@ -307,6 +307,22 @@ int gg_all_score(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, float *out);
  * (generator.py:21) would do with the N x N matrix at sizes where it cannot exist (BASELINE.json configs[4]). */
 int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_t precision, int32_t want_lse, float *row_max,
                         int32_t *row_argmax, float *row_lse, double *kernel_ms_out);
+
+/* gg_topk_scores: streamed top-K retrieval (recommendation).  For each requested node u (rows == NULL: every node, n_rows
+ * ignored; repeated rows allowed) and the table E of model `which` (0 = generator, 1 = discriminator):
+ *   score       s(u, v) = E[u] . E[v], fp32, NO bias (the evaluator's score, link_prediction.py:26-27);
+ *   eligible    exclude = 0: every node; exclude = 1: every node but u itself and u's neighbours in the resident training
+ *               graph (gg_set_graph_csr; duplicates in a list are fine; without a graph: GG_EINVAL);
+ *   result      the first k eligible columns in the order (score descending, column ascending):
+ *               out_col[n_rows][k] (int32) and out_score[n_rows][k] (fp32), row-major; a row with fewer than k eligible
+ *               columns is padded with -1 / -inf.  1 <= k <= 256.
+ * precision 0: exact fp32 (v_mfma_f32_32x32x2_f32, the k-ordered fmaf chain of gg_all_score): indices and scores are those of
+ * a stable sort of the fp32 score rows.  precision 1: a bf16 copy of the table (round to nearest even) on
+ * v_mfma_f32_32x32x16_bf16, fp32 accumulate (n_emb <= 512).  Nothing of size n_rows x n_node exists at any time: rows are
+ * processed in internal passes of 4 096 with bounded device scratch.  kernel_ms_out (may be NULL): HIP-event time of the tile
+ * streams and the device merges, summed over the passes (the bf16 copy excluded, as in gg_all_score_reduce). */
+int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
+                   int32_t *out_col, float *out_score, double *kernel_ms_out);
 
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
