@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgraphgan_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "graphgan_hip.h")
-ABI_VERSION = 8  # == GG_ABI_VERSION of include/graphgan_hip.h (tests/test_host_cpu.py keeps header, binding and library in step)
+ABI_VERSION = 9  # == GG_ABI_VERSION of include/graphgan_hip.h (tests/test_host_cpu.py keeps header, binding and library in step)
 
 
 def header_abi_version(path=HEADER_PATH):
@@ -28,6 +28,7 @@ def header_abi_version(path=HEADER_PATH):
 GG_OK, GG_EINVAL, GG_ECAPACITY, GG_EHIP, GG_ECOMM, GG_ENOMEM, GG_EIO = 0, -1, -2, -3, -4, -5, -6
 GG_OPT_ADAM_DENSE, GG_OPT_ADAM_LAZY, GG_OPT_SGD = 0, 1, 2
 GG_ROOT_OK, GG_ROOT_ABORTED, GG_ROOT_EMPTY = 0, 1, 2
+GG_GS_FOR_D, GG_GS_Q3_STORE = 1, 2
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
                GG_ENOMEM: "GG_ENOMEM", GG_EIO: "GG_EIO"}
 
@@ -113,6 +114,7 @@ SIGNATURES = {
     "gg_all_score": (ctypes.c_int, [_P, _P, _i32, _P]),
     "gg_all_score_reduce": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]),
     "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

@@ -61,3 +61,4 @@ engine_emb_text = True        # write the reference's .emb text after every epoc
 engine_emb_sidecar = False    # also write <emb_filename>.bin: the same fp32 numbers in binary (utils.read_embeddings_bin)
 engine_rec_ks = (2, 10, 20)   # app = "recommendation": the K of the P@K / R@K results line (each in [1, 256])
 engine_rec_precision = "fp32"  # app = "recommendation": ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
+engine_gen_nll = False        # evaluation(): append "gen_nll:NLL=<nll> reach=<reach> n=<n>" -- the held-out NLL of the generator's graph softmax

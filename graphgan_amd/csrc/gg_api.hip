@@ -112,6 +112,7 @@ int alloc_trees(gg_ctx *ctx, const int32_t *roots, int32_t n_roots, const int64_
 // score are stale.  Edge scores are invalidated by moving on to the next epoch (stamps of older epochs never match).
 void generator_changed(gg_ctx *ctx) {
     ctx->dc_valid = false;
+    ctx->gs_es_valid = false;  // (the private scores of gg_graph_softmax as well)
     ctx->es_tick += 256;  // (launches enqueued earlier keep their own ticks: nothing they stamp stays valid)
     ctx->es_valid_from = ctx->es_tick;
 }
@@ -521,7 +522,8 @@ int gg_destroy(gg_ctx *ctx) {
                       &ctx->step_u, &ctx->step_v, &ctx->step_x, &ctx->sg_cnt, &ctx->sg_off, &ctx->sg_slot, &ctx->sg_list, &ctx->sg_rows, &ctx->sg_bias, &ctx->sg_tot, &ctx->sg_key, &ctx->touched_ptr, &ctx->x_cnt, &ctx->x_send_ids, &ctx->x_send_rows,
                       &ctx->x_recv_ids, &ctx->x_recv_rows, &ctx->x_nglob, &ctx->x_own, &ctx->st_item, &ctx->st_item2, &ctx->st_cur, &ctx->st_prev, &ctx->st_len,
                       &ctx->st_alive, &ctx->st_rank, &ctx->bfs_key, &ctx->bfs_bm, &ctx->bfs_misc, &ctx->bfs_sparse, &ctx->bfs_rowptr32, &ctx->lv_pfx, &ctx->dc_keys, &ctx->dc_vals, &ctx->dc_words, &ctx->lv_beg, &ctx->lv_k, &ctx->lv_chunks, &ctx->lv_coff, &ctx->lv_scores, &ctx->lv_chunk_owner, &ctx->lv_prefix, &ctx->lv_big, &ctx->lv_fe, &ctx->fin_list, &ctx->table_bad, &ctx->sgp_cnt, &ctx->sgp_off, &ctx->sgp_slot, &ctx->sgp_list, &ctx->sgp_tot, &ctx->sgp_key, &ctx->sgp_scan, &ctx->sgp_hub, &ctx->sg_hub, &ctx->hub_acc,
-                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj};
+                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj,
+                      &ctx->gs_es, &ctx->gs_cpre};
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->lv_ev)
         if (e) (void)hipEventDestroy(e);
@@ -569,6 +571,7 @@ int gg_set_graph_csr(gg_ctx *ctx, const int64_t *rowptr, const int32_t *col) {
     ctx->bfs_rowptr32_valid = false;
     ctx->topk_adj.release();  // (the sorted copy of gg_topk_scores is rebuilt from the new lists on first use)
     ctx->topk_adj_valid = false;
+    ctx->gs_es_valid = ctx->gs_cpre_valid = false;  // (gg_graph_softmax's edge scores are indexed by the edges of the graph)
     GG_HIP(ctx, hipMalloc((void **)&ctx->g_rowptr, sizeof(int64_t) * (n + 1)));
     GG_HIP(ctx, hipMalloc((void **)&ctx->g_col, sizeof(int32_t) * (std::max<int64_t>(nnz, 1) + 4)));  // (+ 16 B: the BFS reads adjacency in 16-byte quads that may start at the last entry)
     GG_HIP(ctx, hipMemcpy(ctx->g_rowptr, rowptr, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));

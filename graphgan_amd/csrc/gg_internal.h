@@ -294,6 +294,12 @@ struct gg_ctx {
     gg::DevBuf topk_adj;
     bool topk_adj_valid = false;
 
+    // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
+    // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr
+    gg::DevBuf gs_es, gs_cpre;
+    int64_t gs_chunks = 0;
+    bool gs_es_valid = false, gs_cpre_valid = false;
+
     std::string err;
 };
 

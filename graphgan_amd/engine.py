@@ -151,6 +151,8 @@ class Engine:
         self.tree_roots = np.zeros(0, dtype=np.int32)
         self.max_depth = 0
         self._rowptr = None
+        self.tree_mode = (-1, 0)  # (mode, node_cap) of the last set_tree_mode: the library's default until then
+        self.last_graph_softmax_ms = 0.0
 
     # ------------------------------------------------------------------ life cycle
     def close(self):
@@ -192,6 +194,7 @@ class Engine:
         """gg_set_tree_mode: 0 = whole trees, 1 = lazy trees (exact through a level, children lists below it resolved by the
         walks that need them -- same walks, bit for bit), -1 = lazy from 2^18 nodes on (the default)."""
         self._ck(lib.gg_set_tree_mode(self._ctx, int(mode), int(node_cap)))
+        self.tree_mode = (int(mode), int(node_cap))
 
     def lazy_stats(self):
         out = np.zeros(24, dtype=np.int64)
@@ -449,6 +452,55 @@ class Engine:
         self._ck(lib.gg_topk_scores(self._ctx, which, _ptr(rows_a), n_rows, k, {"fp32": 0, "bf16": 1}[precision], int(bool(exclude)),
                                     _ptr(col), _ptr(score), ctypes.byref(ms)))
         return dict(col=col, score=score, kernel_ms=ms.value)
+
+    def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
+        """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node
+        of one walk of ``walk_sample`` on the same slot and mode (graph_gan.py:225-270).  Log-probabilities in fp32, -inf where
+        P = 0 (the root, unreached nodes, dropped fathers).  ``q3_store``: the Q3 bits of the root-batched epochs' store
+        instead of the slots' own.  Returns (logp fp32 [n_slots, N], abort fp32 [n_slots]) -- abort = the mass of walks that
+        end in ``return None, None`` -- or, with ``nodes`` (one array per slot, or a tuple (flat node ids, offsets
+        [n_slots + 1])), (q_logp fp32, abort) with q_logp of the queried nodes (flat, in slot order; per-slot lists: a list of
+        arrays).  The whole trees must be resident (set_tree_mode(0)); time of the sweeps in ``last_graph_softmax_ms``."""
+        slots_a = np.asarray(slots)
+        if slots_a.ndim != 1 or (slots_a.size and not np.issubdtype(slots_a.dtype, np.integer)):
+            raise ValueError("graph_softmax: slots must be a 1-d array of integers")
+        slots_a = _i32(slots_a)
+        R = len(self.tree_roots)
+        if slots_a.size and (int(slots_a.min()) < 0 or int(slots_a.max()) >= R):
+            raise ValueError("graph_softmax: slot outside [0, %d)" % R)
+        ns = len(slots_a)
+        flags = (_lib.GG_GS_FOR_D if for_d else 0) | (_lib.GG_GS_Q3_STORE if q3_store else 0)
+        abort = np.zeros(ns, dtype=np.float32)
+        ms = ctypes.c_double()
+        if nodes is None:
+            logp = np.empty((ns, self.n_node), dtype=np.float32)
+            self._ck(lib.gg_graph_softmax(self._ctx, _ptr(slots_a), ns, flags, _ptr(logp), None, None, None, _ptr(abort), ctypes.byref(ms)))
+            self.last_graph_softmax_ms = ms.value
+            return logp, abort
+        per_slot = isinstance(nodes, list)
+        if per_slot:
+            if len(nodes) != ns:
+                raise ValueError("graph_softmax: %d node lists for %d slots" % (len(nodes), ns))
+            lists = [np.asarray(x).reshape(-1) for x in nodes]
+            off = np.zeros(ns + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in lists], out=off[1:])
+            flat = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        else:
+            if not (isinstance(nodes, tuple) and len(nodes) == 2):
+                raise ValueError("graph_softmax: nodes must be a list of per-slot arrays or a tuple (flat node ids, offsets)")
+            flat, off = np.asarray(nodes[0]).reshape(-1), np.asarray(nodes[1]).reshape(-1)
+            if len(off) != ns + 1 or (len(off) and (off[0] != 0 or off[-1] != len(flat) or np.any(np.diff(off) < 0))):
+                raise ValueError("graph_softmax: offsets must be [n_slots + 1], monotone, from 0 to len(nodes)")
+            off = np.ascontiguousarray(off, dtype=np.int64)
+        if flat.size and (not np.issubdtype(flat.dtype, np.integer) or int(flat.min()) < 0 or int(flat.max()) >= self.n_node):
+            raise ValueError("graph_softmax: node id outside [0, %d)" % self.n_node)
+        flat = _i32(flat)
+        q = np.empty(len(flat), dtype=np.float32)
+        self._ck(lib.gg_graph_softmax(self._ctx, _ptr(slots_a), ns, flags, None, _ptr(off), _ptr(flat), _ptr(q), _ptr(abort), ctypes.byref(ms)))
+        self.last_graph_softmax_ms = ms.value
+        if per_slot:
+            return [q[off[k]:off[k + 1]] for k in range(ns)], abort
+        return q, abort
 
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""

@@ -43,6 +43,7 @@ except ImportError:
 
 from graphgan_amd import _lib, engine as _engine, parallel, utils  # noqa: E402
 from graphgan_amd.evaluation import link_prediction as lp  # noqa: E402
+from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
@@ -409,6 +410,15 @@ class GraphGAN(object):
         with open(cfg.result_filename + ".perf.jsonl", "a") as f:
             f.write(json.dumps(rec) + "\n")
 
+    def gen_likelihood(self):
+        """dict(nll, reach, n): every test edge in both directions under the G-mode distribution of its first node
+        (evaluation/generator_likelihood.py).  Resident trees: the resident slots and their Q3 bits; root batches: whole trees
+        built for batches of test roots with the Q3 bits of the epochs' store (the training's own trees are rebuilt by every
+        epoch_add anyway)."""
+        ev = gl.GenLikelihoodEval(self.config.test_filename, self.n_node, engine=self.engine,
+                                  slot_of_root=self._slot_of_root if self._all_resident else None, batch_roots=self._batch_roots)
+        return ev.eval_gen_likelihood()
+
     @staticmethod
     def evaluation(self):
         cfg = self.config
@@ -428,6 +438,9 @@ class GraphGAN(object):
                 re_ = rec.RecommendEval(cfg.emb_filenames[i], cfg.train_filename, cfg.test_filename, self.n_node, cfg.n_emb,
                                         engine=self.engine, which=i, ks=ks, precision=_cfg(cfg, "engine_rec_precision", "fp32"))
                 results.append(rec.format_results(cfg.modes[i], re_.eval_recommendation(), ks))
+        if _cfg(cfg, "engine_gen_nll", False):
+            # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
+            results.append(gl.format_line(self.gen_likelihood()))
         os.makedirs(os.path.dirname(cfg.result_filename) or ".", exist_ok=True)
         with open(cfg.result_filename, mode="a+") as f:
             f.writelines(results)

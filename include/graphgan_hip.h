@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GG_ABI_VERSION 8  /* gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
+#define GG_ABI_VERSION 9  /* gg_graph_softmax; 8: gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
 
 enum {
     GG_OK = 0,
@@ -323,6 +323,40 @@ int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_
  * streams and the device merges, summed over the passes (the bf16 copy excluded, as in gg_all_score_reduce). */
 int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
                    int32_t *out_col, float *out_score, double *kernel_ms_out);
+
+/* gg_graph_softmax (ABI 9): the generator's distribution G(v | root) of the tree in each given slot, exactly -- the law of the
+ * end node of ONE walk of gg_walk_sample on the same slot, mode and tables.  The reference defines it only by how
+ * GraphGAN.sample walks (graph_gan.py:225-270; scores all_score = E_g E_g^T + b_g, generator.py:21).  With the reference's
+ * lists tree[v] = [father, children...] of the slot's root rho, the candidates N(v) of a reached node v are: at the root its
+ * children (tree[root][1:], :249); elsewhere father + children, the father dropped where the slot's Q3 bit of v is set (a D-mode
+ * walk removed it for good, :258-259) or, with GG_GS_FOR_D, where the father is rho (:256-259).  With
+ *   q(w | v) = exp(s(v, w)) / sum_{x in N(v)} exp(s(v, x)),  s(v, w) = g_v . g_w + b_g[w]      (the mathematical softmax:
+ *   no S2 cut at -28, no S3 truncation -- they differ from it by less than 1e-12)
+ *   reach(rho) = 1, reach(c) = reach(v) q(c | v) for every child c of v;
+ *   P(v) = reach(v) q(father(v) | v) if the father is in N(v), else 0 (P(rho) = 0);
+ *   A = sum of reach(v) over reached v with N(v) empty (the walk aborts, ``return None, None``): a root without children, a
+ *       G-mode depth-1 leaf whose father entry Q3 removed, a D-mode depth-1 leaf (``node_neighbor == [root]``);
+ * sum_v P(v) + A = 1.  Outputs are LOG-probabilities in fp32 (P = 0 -> -inf: the root, unreached nodes, dropped fathers):
+ *   logp       [n_slots * n_node] dense rows by node id, or NULL;
+ *   q_off / q_node / q_logp   queried pairs instead (or as well): q_logp[j] = log P of node q_node[j] in slot k for
+ *              q_off[k] <= j < q_off[k + 1] (q_off[0] = 0; q_off and q_logp both NULL or both given);
+ *   abort_mass [n_slots] A, or NULL.
+ * flags: GG_GS_FOR_D -- the D-mode walk rules; GG_GS_Q3_STORE -- Q3 bits from the persistent store of gg_epoch_* (by root node;
+ * no store yet = no bits) instead of the slots' own rows.
+ * Arithmetic: edge scores in float64 from the fp32 tables (a private buffer filled once per generator state -- the walks' own
+ * edge-score cache is not touched, so walks before and after the call are identical); max, log-sum-exp and log reach in
+ * float64, every sum in a fixed order: a slot's results do not depend on the other slots of the call, their order or the
+ * internal passes of up to 4 096 slots (bounded device scratch), and repeated calls give identical bits.
+ * kernel_ms_out (may be NULL): HIP-event time of the sweeps summed over the passes (the edge-score fill excluded).
+ * GG_EINVAL: lazy resident trees (build them whole: gg_set_tree_mode(ctx, 0) with node_cap 0), trees without edge indices
+ * (gg_get_tree_order's edges_valid == 0), a slot or q_node out of range, a non-finite generator table.  A gg_prepare_g_begin
+ * launch is waited for and dropped (the call reads the trees and the generator). */
+#define GG_GS_FOR_D     1  /* D-mode walk rules */
+#define GG_GS_Q3_STORE  2  /* Q3 bits from the persistent store of gg_epoch_* (no store yet = no bits) instead of the slots' own */
+int gg_graph_softmax(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t flags,
+                     float *logp /*[n_slots * n_node] or NULL*/,
+                     const int64_t *q_off /*[n_slots + 1] or NULL*/, const int32_t *q_node, float *q_logp,
+                     float *abort_mass /*[n_slots] or NULL*/, double *kernel_ms_out);
 
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
