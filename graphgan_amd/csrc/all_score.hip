@@ -18,24 +18,20 @@
 #include <algorithm>
 #include <vector>
 
-#include "gg_internal.h"
+#include "score_tiles.h"
 
 namespace gg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int AS_KC = 32;
-
 __global__ __launch_bounds__(256) void all_score_kernel(const float *E, const float *bias, int n_node, int ld, const int32_t *rows,
                                                         int n_rows, float *out) {
-    __shared__ float As[32][AS_KC + 1];
-    __shared__ float Bs[128][AS_KC + 1];
+    __shared__ float As[32][ST_KC + 1];
+    __shared__ float Bs[128][ST_KC + 1];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int c0 = blockIdx.x * 128, r0 = blockIdx.y * 32;
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    for (int k0 = 0; k0 < ld; k0 += AS_KC) {
+    for (int k0 = 0; k0 < ld; k0 += ST_KC) {
         // stage A: 32 rows x 32 k (one float4 per thread), B: 128 rows x 32 k (four float4 per thread)
         {
             const int r = tid >> 3, kk = (tid & 7) * 4;
@@ -55,20 +51,19 @@ __global__ __launch_bounds__(256) void all_score_kernel(const float *E, const fl
         }
         __syncthreads();
 #pragma unroll
-        for (int kk = 0; kk < AS_KC; kk += 2) {
+        for (int kk = 0; kk < ST_KC; kk += 2) {
             const float a = As[lane & 31][kk + (lane >> 5)];
             const float b = Bs[wv * 32 + (lane & 31)][kk + (lane >> 5)];
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
         }
         __syncthreads();
     }
-    // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     const int col = c0 + wv * 32 + (lane & 31);
     if (col < n_node) {
         const float bj = bias[col];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int row = r0 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+            const int row = r0 + tile_row(reg, lane >> 5);
             if (row < n_rows) out[(int64_t)row * n_node + col] = acc[reg] + bj;
         }
     }
@@ -116,7 +111,7 @@ __device__ __forceinline__ void run_merge(Running &a, float m, float s, int arg,
 }
 
 // merge the 16 per-lane cells of a wave over its 32 column lanes (lanes l and l ^ 32 hold different rows) and the
-// 4 waves of the workgroup through LDS; rows of the tile: row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+// 4 waves of the workgroup through LDS
 template <int NR>
 __device__ __forceinline__ void tile_finish(Running (&run)[NR], bool lse, int rows_base, int n_rows, int split, int n_splits, float *part_max,
                                             int32_t *part_arg, float *part_sum, float (*sh_m)[32 * (NR / 16)], float (*sh_s)[32 * (NR / 16)],
@@ -132,7 +127,7 @@ __device__ __forceinline__ void tile_finish(Running (&run)[NR], bool lse, int ro
         }
         if ((lane & 31) == 0) {
             const int rb = i / 16, reg = i % 16;
-            const int row = rb * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+            const int row = rb * 32 + tile_row(reg, lane >> 5);
             sh_m[wv][row] = run[i].m;
             sh_s[wv][row] = run[i].s;
             sh_a[wv][row] = run[i].arg;
@@ -151,72 +146,56 @@ __device__ __forceinline__ void tile_finish(Running (&run)[NR], bool lse, int ro
     }
 }
 
+// The consumer of both streams: per lane the running cells of the 16 RB (row, column-lane) pairs it owns.  The cells are an
+// array of the KERNEL that the consumer refers to (as a member array, the bf16 kernels took up to 56 registers more and
+// <4, 2> lost a wave per SIMD).
+template <int RB>
+struct RowStats {
+    Running (&run)[16 * RB];
+    const float *bias;
+    const bool lse;
+    __device__ __forceinline__ RowStats(Running (&run_)[16 * RB], const float *bias_, bool lse_) : run(run_), bias(bias_), lse(lse_) {}
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int i = 0; i < 16 * RB; ++i) run[i] = Running{-INFINITY, 0.f, 0x7fffffff};
+    }
+    // fp32 stream: the bias is added to the finished dot product (the arithmetic of gg_all_score)
+    __device__ __forceinline__ void operator()(const f32x16 &acc, int col, bool ok) {
+        if (ok) {
+            const float bj = bias[col];
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) run_update(run[reg], acc[reg] + bj, col, lse);
+        }
+    }
+    // bf16 stream: the accumulators START at the column's bias -- S = b + sum_k, the order the x32 kernel below computes in: same bits
+    __device__ __forceinline__ float start(int col, bool ok) const { return ok ? bias[col] : 0.f; }
+    __device__ __forceinline__ void operator()(const f32x16 (&acc)[RB], int col, bool ok) {
+        if (ok) {
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) run_update(run[rb * 16 + reg], acc[rb][reg], col, lse);
+        }
+    }
+};
+
 __global__ __launch_bounds__(256) void all_score_reduce_f32_kernel(const float *E, const float *bias, int n_node, int ld, const int32_t *rows,
                                                                    int n_rows, int cols_per_split, int lse, float *part_max, int32_t *part_arg,
                                                                    float *part_sum) {
     extern __shared__ float As_all[];  // [32][ld + 1]: the tile's 32 rows, staged once
-    __shared__ float Bs[128][AS_KC + 1];
+    __shared__ float Bs[128][ST_KC + 1];
     __shared__ float sh_m[4][32], sh_s[4][32];
     __shared__ int sh_a[4][32];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int split = blockIdx.x, r0 = blockIdx.y * 32;
-    const int lda = ld + 1;
-    for (int i = tid; i < 32 * (ld / 4); i += 256) {
-        const int r = i / (ld / 4), kk = (i % (ld / 4)) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r0 + r < n_rows) {
-            const int node = rows ? rows[r0 + r] : r0 + r;
-            v = *(const float4 *)(E + (int64_t)node * ld + kk);
-        }
-        float *d = As_all + r * lda + kk;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    Running run[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) run[i] = Running{-INFINITY, 0.f, 0x7fffffff};
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    for (int c0 = cbeg; c0 < cend; c0 += 128) {
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        for (int k0 = 0; k0 < ld; k0 += AS_KC) {
-            __syncthreads();  // also orders the A staging before its first use
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = (tid >> 3) + 32 * i, kk = (tid & 7) * 4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (c0 + r < cend && k0 + kk < ld) v = *(const float4 *)(E + (int64_t)(c0 + r) * ld + k0 + kk);
-                Bs[r][kk] = v.x; Bs[r][kk + 1] = v.y; Bs[r][kk + 2] = v.z; Bs[r][kk + 3] = v.w;
-            }
-            __syncthreads();
-            const int kmax = min(AS_KC, ld - k0);
-            for (int kk = 0; kk < kmax; kk += 2) {
-                const float a = As_all[(lane & 31) * lda + k0 + kk + (lane >> 5)];
-                const float b = Bs[wv * 32 + (lane & 31)][kk + (lane >> 5)];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-            }
-        }
-        const int col = c0 + wv * 32 + (lane & 31);
-        if (col < cend) {
-            const float bj = bias[col];
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) run_update(run[reg], acc[reg] + bj, col, lse != 0);
-        }
-    }
+    Running run[16];
+    RowStats<1> stats(run, bias, lse != 0);
+    f32_score_tiles(E, ld, rows, n_rows, r0, cbeg, cend, As_all, Bs, stats);
     __syncthreads();
     tile_finish<16>(run, lse != 0, r0, n_rows, split, gridDim.x, part_max, part_arg, part_sum, sh_m, sh_s, sh_a);
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// fp32 table -> bf16 copy (round to nearest even, k zero padded to ld16 = 16 KS, rows zero padded to a multiple of 32), TILED for
-// the matrix instruction's B operand: the 16-byte piece {k = 16 s + 8 h .. + 8} of row r sits at piece index
-//     ((r / 32) * KS + s) * 64 + 32 h + r % 32,
-// i.e. the 64 lanes of a wavefront that loads k-step s of a 32-column tile (lane = 32 h + column) read ONE CONTIGUOUS KILOBYTE.
-// (Row-major, every such load touched 32 different cache lines for 32 bytes each: 4 wavefronts x 16 loads x 32 line look-ups per
-// tile and CU were what the wide consumer waited for, not the HBM and not the matrix pipe.)
-__device__ __forceinline__ int64_t bf16_piece(int64_t r, int s, int h, int KS) { return ((r >> 5) * KS + s) * 64 + 32 * h + (r & 31); }
-
+// fp32 table -> its tiled bf16 copy (score_tiles.h, bf16_piece)
 __global__ void to_bf16_kernel(const float *E, int64_t n, int64_t n_pad, int ld, int ld16, __bf16 *out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pad * ld16) return;
@@ -226,65 +205,17 @@ __global__ void to_bf16_kernel(const float *E, int64_t n, int64_t n_pad, int ld,
     out[bf16_piece(r, k >> 4, (k >> 3) & 1, ld16 / 16) * 8 + (k & 7)] = (__bf16)v;
 }
 
-// KS = ld16 / 16 k-steps, RB row blocks of 32 rows per workgroup.  No LDS for the operands: the A fragments of the
-// tile's rows stay in registers for the whole column sweep, every lane streams the 8-element k-slices of its own column
-// straight from the bf16 table (16 bytes per load; the two half-waves read the two halves of a 32-byte piece).
+// KS = ld16 / 16 k-steps, RB row blocks of 32 rows per workgroup; the next tile is prefetched for every KS (two waves per SIMD).
 template <int KS, int RB>
 __global__ __launch_bounds__(256) void all_score_reduce_bf16_kernel(const uint4 *Eb, const float *bias, int n_node, const int32_t *rows, int n_rows,
                                                                     int cols_per_split, int lse, float *part_max, int32_t *part_arg, float *part_sum) {
     __shared__ float sh_m[4][32 * RB], sh_s[4][32 * RB];
     __shared__ int sh_a[4][32 * RB];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5;
     const int split = blockIdx.x, r0 = blockIdx.y * (32 * RB);
-    union Frag { uint4 u; bf16x8 v; };
-    Frag afrag[RB][KS];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const int r = r0 + rb * 32 + (lane & 31);
-        const int node = r < n_rows ? (rows ? rows[r] : r) : -1;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) afrag[rb][s].u = node >= 0 ? Eb[bf16_piece(node, s, half, KS)] : make_uint4(0u, 0u, 0u, 0u);
-    }
-    Running run[16 * RB];
-#pragma unroll
-    for (int i = 0; i < 16 * RB; ++i) run[i] = Running{-INFINITY, 0.f, 0x7fffffff};
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    // B fragments are double buffered in registers: the KS loads of the NEXT 32-column tile are issued before the matrix
-    // instructions and the consumer of the current one, so that memory latency hides behind them (two waves per SIMD).
-    Frag bcur[KS], bnxt[KS];
-    auto load_tile = [&](Frag (&dst)[KS], int c0t) {
-        // (tiles start at multiples of 32 columns; the padded rows behind the table's end are zeros; a prefetch behind the
-        // split's end re-reads its first tile)
-        const uint4 *brow = Eb + (int64_t)((c0t < cend ? c0t : cbeg) >> 5) * KS * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) dst[s].u = brow[64 * s];
-    };
-    load_tile(bcur, cbeg + wv * 32);
-    for (int c0 = cbeg + wv * 32; c0 < cend; c0 += 128) {
-        const int col = c0 + (lane & 31);
-        const bool ok = col < cend;
-        load_tile(bnxt, c0 + 128);
-        // (the accumulators START at the column's bias -- S = b + sum_k, the order the x32 kernel below computes in: same bits)
-        const float bj = ok ? bias[col] : 0.f;
-        f32x16 acc[RB];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[rb][i] = bj;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[rb][s].v, bcur[s].v, acc[rb], 0, 0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < KS; ++s) bcur[s] = bnxt[s];
-        if (ok) {
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) run_update(run[rb * 16 + reg], acc[rb][reg], col, lse != 0);
-        }
-    }
+    Running run[16 * RB];
+    RowStats<RB> stats(run, bias, lse != 0);
+    bf16_score_tiles<KS, RB, true>(Eb, rows, n_rows, r0, cbeg, cend, stats);
     tile_finish<16 * RB>(run, lse != 0, r0, n_rows, split, gridDim.x, part_max, part_arg, part_sum, sh_m, sh_s, sh_a);
 }
 
@@ -565,6 +496,36 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
     }
 }
 
+// ---- the host plan of score_tiles.h ----
+
+int check_row_ids(gg_ctx *ctx, const char *entry, const int32_t *rows, int n_rows) {
+    if (rows)
+        for (int i = 0; i < n_rows; ++i) GG_CHECK(ctx, rows[i] >= 0 && rows[i] < ctx->n_node, GG_EINVAL, "%s: row id %d out of range", entry, rows[i]);
+    return GG_OK;
+}
+
+Bf16Shape bf16_shape(int n_emb) {
+    const int ks_need = (n_emb + 15) / 16;
+    const int KS = ks_need <= 4 ? 4 : ks_need <= 8 ? 8 : ks_need <= 16 ? 16 : 32;
+    return {KS, 16 * KS};
+}
+
+ColumnSplit column_split(int n_node, int row_tiles, int target_workgroups, int max_splits) {
+    const int want = std::max(1, std::min({cdiv(n_node, 128), cdiv(target_workgroups, row_tiles), max_splits}));
+    const int cps = cdiv(cdiv(n_node, want), 128) * 128;
+    return {cdiv(n_node, cps), cps};
+}
+
+hipError_t bf16_table(gg_ctx *ctx, int which, int ld16, DevBuf &buf) {
+    const int64_t n_pad = ((int64_t)ctx->n_node + 31) / 32 * 32;  // the copy is tiled by 32 rows
+    const int64_t tot = n_pad * ld16;
+    const hipError_t e = buf.reserve(sizeof(uint16_t) * (size_t)tot);
+    if (e == hipSuccess)
+        hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, ctx->model[which].E, (int64_t)ctx->n_node, n_pad,
+                           ctx->ld, ld16, (__bf16 *)buf.p);
+    return e;
+}
+
 }  // namespace gg
 
 using namespace gg;
@@ -575,8 +536,7 @@ extern "C" int gg_all_score(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, fl
     if (!rows) n_rows = ctx->n_node;
     if (n_rows == 0) return GG_OK;
     const int n = ctx->n_node;
-    if (rows)
-        for (int i = 0; i < n_rows; ++i) GG_CHECK(ctx, rows[i] >= 0 && rows[i] < n, GG_EINVAL, "gg_all_score: row id %d out of range", rows[i]);
+    if (const int rc = check_row_ids(ctx, "gg_all_score", rows, n_rows)) return rc;
     GG_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf d_rows, d_out;
     hipError_t e = d_out.reserve(sizeof(float) * (size_t)n_rows * n);
@@ -598,34 +558,22 @@ extern "C" int gg_all_score(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, fl
     return GG_OK;
 }
 
-// gg_all_score_reduce: see include/graphgan_hip.h.
-extern "C" int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_t precision, int32_t want_lse, float *row_max,
-                                   int32_t *row_argmax, float *row_lse, double *kernel_ms_out) {
-    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    GG_CHECK(ctx, n_rows >= 0 && row_max && row_argmax && (row_lse || !want_lse), GG_EINVAL, "gg_all_score_reduce: bad argument");
-    GG_CHECK(ctx, precision == 0 || precision == 1, GG_EINVAL, "gg_all_score_reduce: precision must be 0 (fp32) or 1 (bf16)");
-    if (!rows) n_rows = ctx->n_node;
-    if (n_rows == 0) return GG_OK;
+// One pass of gg_all_score_reduce over validated arguments (rows == NULL: n_rows = n_node).  allow_wide: many bf16 rows may take
+// the x32 kernel; if its reference-free sum left the fp32 range, *overflowed is set and no result is written.
+static int reduce_once(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_t precision, int32_t want_lse, float *row_max, int32_t *row_argmax,
+                       float *row_lse, double *kernel_ms_out, bool allow_wide, bool *overflowed) {
     const int n = ctx->n_node, ld = ctx->ld;
-    if (rows)
-        for (int i = 0; i < n_rows; ++i) GG_CHECK(ctx, rows[i] >= 0 && rows[i] < n, GG_EINVAL, "gg_all_score_reduce: row id %d out of range", rows[i]);
-    GG_HIP(ctx, hipSetDevice(ctx->device));
-    // k-steps of 16 bf16 elements; the kernel is instantiated for 4 / 8 / 16 / 32 of them: the copy is zero padded to that
-    const int ks_need = (ctx->n_emb + 15) / 16;
-    const int KS = ks_need <= 4 ? 4 : ks_need <= 8 ? 8 : ks_need <= 16 ? 16 : 32;
-    const int ld16 = 16 * KS;
+    const Bf16Shape bs = bf16_shape(ctx->n_emb);
+    const int KS = bs.KS;
     const int RB = (precision == 1 && KS <= 8) ? 2 : 1;
     // bf16, many rows: the x32 kernel -- a workgroup's wavefronts take 32 RB rows each and share ONE sweep of the table, one
     // workgroup per compute unit (all_score_reduce_bf16_x32_kernel)
-    static thread_local bool force_narrow = false;  // set for the repeat of a call whose wide kernel reported an overflowing sum
-    const bool wide = precision == 1 && n_rows >= 512 && !getenv("GG_ALLPAIRS_NARROW") && !force_narrow;
+    const bool wide = allow_wide && precision == 1 && n_rows >= 512 && !getenv("GG_ALLPAIRS_NARROW");
     static const bool one_wave = getenv("GG_K7_NW4") != nullptr;  // (A/B at d <= 256: one wavefront per SIMD with 4 row blocks)
     const int tile_rows = wide ? (KS <= 16 ? 512 : 256) : 32 * RB;  // (x32: 32 RB NW rows)
     const int row_tiles = cdiv(n_rows, tile_rows);
-    // enough workgroups for the chip: split the columns when there are few row tiles (multiples of 128 columns)
-    int splits = std::max(1, std::min(cdiv(n, 128), cdiv(wide ? 256 : 2048, row_tiles)));
-    int cps = cdiv(cdiv(n, splits), 128) * 128;
-    splits = cdiv(n, cps);
+    const ColumnSplit cs = column_split(n, row_tiles, wide ? 256 : 2048);
+    const int splits = cs.splits, cps = cs.cols_per_split;
     DevBuf d_rows, d_pm, d_pa, d_ps, d_bf, d_ovf;
     auto rel = [&]() { d_rows.release(); d_pm.release(); d_pa.release(); d_ps.release(); d_bf.release(); d_ovf.release(); };
     const size_t np = (size_t)n_rows * splits;
@@ -633,19 +581,14 @@ extern "C" int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_r
     if (e == hipSuccess) e = d_pa.reserve(sizeof(int32_t) * np);
     if (e == hipSuccess) e = d_ps.reserve(sizeof(float) * np);
     if (e == hipSuccess && rows) e = d_rows.reserve(sizeof(int32_t) * n_rows);
-    const int64_t n_pad = ((int64_t)n + 31) / 32 * 32;  // the bf16 copy is tiled by 32 rows
-    if (e == hipSuccess && precision == 1) e = d_bf.reserve(sizeof(uint16_t) * (size_t)n_pad * ld16);
     if (e == hipSuccess) e = d_ovf.reserve(sizeof(int32_t) * 4);
+    if (e == hipSuccess && precision == 1) e = bf16_table(ctx, 0, bs.ld16, d_bf);
     if (e != hipSuccess) { rel(); return fail(ctx, GG_ENOMEM, "gg_all_score_reduce: %s", hipGetErrorString(e)); }
     (void)hipMemsetAsync(d_ovf.p, 0, sizeof(int32_t) * 4, ctx->stream);
     if (rows) (void)hipMemcpyAsync(d_rows.p, rows, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, ctx->stream);
     const Model &G = ctx->model[0];
     const int32_t *dr = rows ? d_rows.as<int32_t>() : nullptr;
     const dim3 grid(splits, row_tiles);
-    if (precision == 1) {
-        const int64_t tot = n_pad * ld16;
-        hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, G.E, (int64_t)n, n_pad, ld, ld16, (__bf16 *)d_bf.p);
-    }
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     if (precision == 0) {
         const size_t dyn = sizeof(float) * 32 * (size_t)(ld + 1);
@@ -711,12 +654,10 @@ extern "C" int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_r
     int32_t h_ovf = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&h_ovf, d_ovf.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && h_ovf && wide) {  // scores outside the range of the wide kernel's reference-free sum: running-max kernel
+    if (e == hipSuccess && h_ovf && wide) {  // scores outside the range of the wide kernel's reference-free sum
         rel();
-        force_narrow = true;
-        const int rc = gg_all_score_reduce(ctx, rows, rows ? n_rows : 0, precision, want_lse, row_max, row_argmax, row_lse, kernel_ms_out);
-        force_narrow = false;
-        return rc;
+        *overflowed = true;
+        return GG_OK;
     }
     float ms = 0.f;
     if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
@@ -741,4 +682,21 @@ extern "C" int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_r
         if (want_lse) row_lse[r] = (float)((double)M + log(S));
     }
     return GG_OK;
+}
+
+// gg_all_score_reduce: see include/graphgan_hip.h.
+extern "C" int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_t precision, int32_t want_lse, float *row_max,
+                                   int32_t *row_argmax, float *row_lse, double *kernel_ms_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    GG_CHECK(ctx, n_rows >= 0 && row_max && row_argmax && (row_lse || !want_lse), GG_EINVAL, "gg_all_score_reduce: bad argument");
+    GG_CHECK(ctx, precision == 0 || precision == 1, GG_EINVAL, "gg_all_score_reduce: precision must be 0 (fp32) or 1 (bf16)");
+    if (!rows) n_rows = ctx->n_node;
+    if (n_rows == 0) return GG_OK;
+    if (const int rc = check_row_ids(ctx, "gg_all_score_reduce", rows, n_rows)) return rc;
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    bool overflowed = false, again = false;
+    int rc = reduce_once(ctx, rows, n_rows, precision, want_lse, row_max, row_argmax, row_lse, kernel_ms_out, true, &overflowed);
+    // the wide kernel's sum left the fp32 range: once more with the narrow kernel (running maximum per cell: it cannot overflow)
+    if (rc == GG_OK && overflowed) rc = reduce_once(ctx, rows, n_rows, precision, want_lse, row_max, row_argmax, row_lse, kernel_ms_out, false, &again);
+    return rc;
 }

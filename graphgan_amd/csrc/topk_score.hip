@@ -18,27 +18,25 @@
 // in place; the new K-th key becomes the row's tau.  A wavefront's columns only grow, so a candidate never ties a list entry.
 // topk_merge_kernel then merges the (split, wavefront) lists of a row on the device (one workgroup per row, rank merge in LDS,
 // a list whose head does not beat the running K-th key is skipped).
-//   fp32: v_mfma_f32_32x32x2_f32 with the tile staging of all_score_reduce_f32_kernel -- the same k-ordered fmaf chain from
-//         0.0, so the scores are bit-identical to gg_all_score (zero bias) and the oracle's rows;
-//   bf16: v_mfma_f32_32x32x16_bf16 on a bf16 copy of the table (round to nearest even, K7's tiled layout), fp32 accumulate;
-//         the requested rows' fragments stay in registers, every lane streams its own column's k-slices.
+// The tiles come from the producers K7's streamed consumer uses (score_tiles.h):
+//   fp32: f32_score_tiles -- the k-ordered fmaf chain from 0.0, so the scores are bit-identical to gg_all_score (zero bias)
+//         and the oracle's rows;
+//   bf16: bf16_score_tiles on the tiled bf16 copy of the table (round to nearest even), fp32 accumulate from 0.0; the next
+//         tile is prefetched while its fragments fit (KS <= 16).
 #include <math.h>
 
 #include <algorithm>
 #include <thread>
 #include <vector>
 
-#include "gg_internal.h"
+#include "score_tiles.h"
 
 namespace gg {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
 
-constexpr int TK_KC = 32;          // k-chunk of the fp32 tile staging (as K7)
 constexpr int TK_CHUNK = 4096;     // requested rows per internal pass
 constexpr int TK_MAX_K = 256;
 constexpr size_t TK_PART_CAP = size_t(256) << 20;  // bytes of partial lists per pass, at most
@@ -133,7 +131,7 @@ __device__ __forceinline__ bool adj_contains(const int32_t *a, int64_t n, int co
 }
 
 // Per wavefront: the k-lists of the tile's 32 rows (sub-list `sub`) and, per lane, tau of the 16 rows it holds
-// (row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), the matrix instruction's C layout).
+// (tile_row(reg, lane >> 5), the matrix instruction's C layout).
 struct WaveLists {
     float tau[16];
 };
@@ -150,7 +148,7 @@ __device__ __forceinline__ void lists_init(WaveLists &st, const TopkOut &o, int 
     __threadfence_block();
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int row = r0 + (reg & 3) + 8 * (reg >> 2) + 4 * hi;
+        const int row = r0 + tile_row(reg, hi);
         st.tau[reg] = row < o.n_rows ? -INFINITY : INFINITY;  // (rows behind the pass never take a candidate)
     }
 }
@@ -176,7 +174,7 @@ __device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, i
 #pragma unroll 1
         for (int h = 0; h < 2; ++h) {
             if (((pm >> (32 * h)) & 0xffffffffull) == 0) continue;
-            const int row = r0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            const int row = r0 + tile_row(reg, h);
             bool cand = p && hi == h;
             if (cand && o.adj) {
                 const int u = o.rows[row];
@@ -191,101 +189,36 @@ __device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, i
     }
 }
 
+// The consumer handed to the producers of score_tiles.h: the wavefront's lists of the tile's rows; scores carry no bias.
+// init() (the lists' global stores) runs BEHIND the staging of the requested rows: in front of it, the exclusion test's loads of
+// o.rows / o.adj_ptr stopped being scalar loads and fp32 with exclude = 1 ran 4 % slower.
+struct ListConsumer {
+    WaveLists st;
+    const TopkOut &o;
+    const int r0, sub;
+    __device__ __forceinline__ ListConsumer(const TopkOut &o_, int r0_, int sub_) : o(o_), r0(r0_), sub(sub_) {}
+    __device__ __forceinline__ void init() { lists_init(st, o, r0, sub); }
+    __device__ __forceinline__ float start(int, bool) const { return 0.f; }
+    __device__ __forceinline__ void operator()(const f32x16 &acc, int col, bool ok) { lists_consume(st, o, r0, sub, acc, col, ok); }
+    __device__ __forceinline__ void operator()(const f32x16 (&acc)[1], int col, bool ok) { lists_consume(st, o, r0, sub, acc[0], col, ok); }
+};
+
 __global__ __launch_bounds__(256) void topk_f32_kernel(const float *E, int n_node, int ld, int cols_per_split, TopkOut o) {
     extern __shared__ float As_all[];  // [32][ld + 1]: the tile's 32 requested rows, staged once
-    __shared__ float Bs[128][TK_KC + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + wv;
-    const int lda = ld + 1;
-    for (int i = tid; i < 32 * (ld / 4); i += 256) {
-        const int r = i / (ld / 4), kk = (i % (ld / 4)) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r0 + r < o.n_rows) v = *(const float4 *)(E + (int64_t)o.rows[r0 + r] * ld + kk);
-        float *d = As_all + r * lda + kk;
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    WaveLists st;
-    lists_init(st, o, r0, sub);
+    __shared__ float Bs[128][ST_KC + 1];
+    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + (threadIdx.x >> 6);
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    for (int c0 = cbeg; c0 < cend; c0 += 128) {
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        for (int k0 = 0; k0 < ld; k0 += TK_KC) {
-            __syncthreads();  // also orders the A staging before its first use
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = (tid >> 3) + 32 * i, kk = (tid & 7) * 4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (c0 + r < cend && k0 + kk < ld) v = *(const float4 *)(E + (int64_t)(c0 + r) * ld + k0 + kk);
-                Bs[r][kk] = v.x; Bs[r][kk + 1] = v.y; Bs[r][kk + 2] = v.z; Bs[r][kk + 3] = v.w;
-            }
-            __syncthreads();
-            const int kmax = min(TK_KC, ld - k0);
-            for (int kk = 0; kk < kmax; kk += 2) {
-                const float a = As_all[(lane & 31) * lda + k0 + kk + (lane >> 5)];
-                const float b = Bs[wv * 32 + (lane & 31)][kk + (lane >> 5)];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-            }
-        }
-        const int col = c0 + wv * 32 + (lane & 31);
-        lists_consume(st, o, r0, sub, acc, col, col < cend);
-    }
+    ListConsumer lists(o, r0, sub);
+    f32_score_tiles(E, ld, o.rows, o.n_rows, r0, cbeg, cend, As_all, Bs, lists);
 }
 
-// K7's tiled bf16 layout (all_score.hip, bf16_piece): the 16-byte piece {k = 16 s + 8 h .. + 8} of row r at piece index
-// ((r / 32) KS + s) 64 + 32 h + r % 32 -- the 64 lanes that load k-step s of a 32-column tile read one contiguous kilobyte.
-__device__ __forceinline__ int64_t tk_piece(int64_t r, int s, int h, int KS) { return ((r >> 5) * KS + s) * 64 + 32 * h + (r & 31); }
-
-__global__ void topk_to_bf16_kernel(const float *E, int64_t n, int64_t n_pad, int ld, int ld16, __bf16 *out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pad * ld16) return;
-    const int64_t r = i / ld16;
-    const int k = (int)(i % ld16);
-    const float v = (r < n && k < ld) ? E[r * ld + k] : 0.0f;
-    out[tk_piece(r, k >> 4, (k >> 3) & 1, ld16 / 16) * 8 + (k & 7)] = (__bf16)v;
-}
-
-// KS k-steps of 16.  The A fragments of the tile's 32 requested rows stay in registers for the whole sweep; every lane streams
-// the k-slices of its own column (B), double buffered while they fit (KS <= 16).
+// KS k-steps of 16; the next tile's B fragments are prefetched while they fit (KS <= 16).
 template <int KS>
 __global__ __launch_bounds__(256) void topk_bf16_kernel(const uint4 *Eb, int n_node, int cols_per_split, TopkOut o) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5;
-    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + wv;
-    union Frag { uint4 u; bf16x8 v; };
-    Frag afrag[KS];
-    {
-        const int r = r0 + (lane & 31);
-        const int node = r < o.n_rows ? o.rows[r] : -1;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) afrag[s].u = node >= 0 ? Eb[tk_piece(node, s, half, KS)] : make_uint4(0u, 0u, 0u, 0u);
-    }
-    WaveLists st;
-    lists_init(st, o, r0, sub);
+    const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + (threadIdx.x >> 6);
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    constexpr bool PF = KS <= 16;
-    Frag bcur[KS], bnxt[PF ? KS : 1];
-    auto load_tile = [&](Frag *dst, int c0t) {  // (a prefetch behind the split's end re-reads its first tile)
-        const uint4 *brow = Eb + (int64_t)((c0t < cend ? c0t : cbeg) >> 5) * KS * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) dst[s].u = brow[64 * s];
-    };
-    if (PF) load_tile(bcur, cbeg + wv * 32);
-    for (int c0 = cbeg + wv * 32; c0 < cend; c0 += 128) {
-        const int col = c0 + (lane & 31);
-        if (PF) load_tile(bnxt, c0 + 128);
-        else load_tile(bcur, c0);
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[s].v, bcur[s].v, acc, 0, 0, 0);
-        if (PF) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s) bcur[s] = bnxt[PF ? s : 0];
-        }
-        lists_consume(st, o, r0, sub, acc, col, col < cend);
-    }
+    ListConsumer lists(o, r0, sub);
+    bf16_score_tiles<KS, 1, (KS <= 16)>(Eb, o.rows, o.n_rows, r0, cbeg, cend, lists);
 }
 
 // Count of keys > x in a descending list of k keys.
@@ -371,31 +304,23 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
     GG_CHECK(ctx, out_col && out_score && (rows || n_rows >= 0) && n_rows >= 0, GG_EINVAL, "gg_topk_scores: bad argument");
     GG_CHECK(ctx, !exclude || ctx->g_rowptr, GG_EINVAL, "gg_topk_scores: exclude = 1 needs the training graph (gg_set_graph_csr)");
     const int n = ctx->n_node, ld = ctx->ld;
-    // bf16: k-steps of 16 elements, instantiated for 4 / 8 / 16 / 32 of them (the copy is zero padded to that)
-    const int ks_need = (ctx->n_emb + 15) / 16;
-    GG_CHECK(ctx, precision == 0 || ks_need <= 32, GG_EINVAL, "gg_topk_scores: bf16 supports n_emb <= 512 (got %d)", ctx->n_emb);
+    GG_CHECK(ctx, precision == 0 || ctx->n_emb <= 512, GG_EINVAL, "gg_topk_scores: bf16 supports n_emb <= 512 (got %d)", ctx->n_emb);
     const size_t dyn = sizeof(float) * 32 * (size_t)(ld + 1);
     GG_CHECK(ctx, precision == 1 || dyn <= 140 * 1024, GG_EINVAL, "gg_topk_scores: fp32 supports n_emb <= 1116 (got %d)", ctx->n_emb);
     if (!rows) n_rows = n;
     if (kernel_ms_out) *kernel_ms_out = 0.0;
     if (n_rows == 0) return GG_OK;
-    if (rows)
-        for (int i = 0; i < n_rows; ++i) GG_CHECK(ctx, rows[i] >= 0 && rows[i] < n, GG_EINVAL, "gg_topk_scores: row id %d out of range", rows[i]);
+    if (const int rc = check_row_ids(ctx, "gg_topk_scores", rows, n_rows)) return rc;
     GG_HIP(ctx, hipSetDevice(ctx->device));
     if (exclude) {
         const int rc = ensure_sorted_adjacency(ctx);
         if (rc != GG_OK) return rc;
     }
-    const int KS = ks_need <= 4 ? 4 : ks_need <= 8 ? 8 : ks_need <= 16 ? 16 : 32;
-    const int ld16 = 16 * KS;
+    const Bf16Shape bs = bf16_shape(ctx->n_emb);
     const int chunk = std::min(n_rows, TK_CHUNK);
-    const int row_tiles_max = cdiv(chunk, 32);
-    // enough workgroups for the chip (multiples of 128 columns per split), the partial lists of a pass within TK_PART_CAP
-    int splits = std::max(1, std::min(cdiv(n, 128), cdiv(2048, row_tiles_max)));
-    splits = std::max(1, std::min<int>(splits, (int)(TK_PART_CAP / ((size_t)chunk * 4 * k * sizeof(u64)))));
-    const int cps = cdiv(cdiv(n, splits), 128) * 128;
-    splits = cdiv(n, cps);
-    const int n_sub = 4 * splits;
+    // column splits as K7's, the partial lists of a pass (4 per split and row) within TK_PART_CAP
+    const ColumnSplit cs = column_split(n, cdiv(chunk, 32), 2048, (int)(TK_PART_CAP / ((size_t)chunk * 4 * k * sizeof(u64))));
+    const int splits = cs.splits, cps = cs.cols_per_split, n_sub = 4 * splits;
     const Model &M = ctx->model[which];
     DevBuf d_rows, d_part, d_col, d_score, d_bf;
     auto rel = [&]() { d_rows.release(); d_part.release(); d_col.release(); d_score.release(); d_bf.release(); };
@@ -403,16 +328,9 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
     if (e == hipSuccess) e = d_part.reserve(sizeof(u64) * (size_t)chunk * n_sub * k);
     if (e == hipSuccess) e = d_col.reserve(sizeof(int32_t) * (size_t)chunk * k);
     if (e == hipSuccess) e = d_score.reserve(sizeof(float) * (size_t)chunk * k);
-    const int64_t n_pad = ((int64_t)n + 31) / 32 * 32;  // the bf16 copy is tiled by 32 rows
-    if (e == hipSuccess && precision == 1) e = d_bf.reserve(sizeof(uint16_t) * (size_t)n_pad * ld16);
+    if (e == hipSuccess && precision == 1) e = bf16_table(ctx, which, bs.ld16, d_bf);
     if (e != hipSuccess) { rel(); return fail(ctx, GG_ENOMEM, "gg_topk_scores: %s", hipGetErrorString(e)); }
-    if (precision == 1) {
-        const int64_t tot = n_pad * ld16;
-        hipLaunchKernelGGL(topk_to_bf16_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, M.E, (int64_t)n, n_pad, ld, ld16,
-                           (__bf16 *)d_bf.p);
-    } else if (dyn > 48 * 1024) {
-        (void)hipFuncSetAttribute((const void *)topk_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    }
+    if (precision == 0 && dyn > 48 * 1024) (void)hipFuncSetAttribute((const void *)topk_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     std::vector<int32_t> ids;
     double ms_total = 0.0;
     for (int c0 = 0; c0 < n_rows && e == hipSuccess; c0 += chunk) {
@@ -432,9 +350,9 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
             hipLaunchKernelGGL(topk_f32_kernel, grid, dim3(256), dyn, ctx->stream, M.E, n, ld, cps, o);
         } else {
             const uint4 *Eb = (const uint4 *)d_bf.p;
-            if (KS == 4) hipLaunchKernelGGL(topk_bf16_kernel<4>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
-            else if (KS == 8) hipLaunchKernelGGL(topk_bf16_kernel<8>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
-            else if (KS == 16) hipLaunchKernelGGL(topk_bf16_kernel<16>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            if (bs.KS == 4) hipLaunchKernelGGL(topk_bf16_kernel<4>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            else if (bs.KS == 8) hipLaunchKernelGGL(topk_bf16_kernel<8>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+            else if (bs.KS == 16) hipLaunchKernelGGL(topk_bf16_kernel<16>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
             else hipLaunchKernelGGL(topk_bf16_kernel<32>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
         }
         hipLaunchKernelGGL(topk_merge_kernel, dim3(cr), dim3(256), 0, ctx->stream, (const u64 *)d_part.p, n_sub, k, d_col.as<int32_t>(), d_score.as<float>());

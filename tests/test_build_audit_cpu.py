@@ -1,5 +1,6 @@
-"""Build audits.  The wide all-pairs kernel (graphgan_amd/csrc/all_score.hip, all_score_reduce_bf16_x32_kernel) must keep its
-operands in registers: the build fails if an instantiation uses scratch (csrc/check_no_scratch.sh) -- checked here on the
+"""Build audits.  The kernels that must keep their operands in registers -- the wide all-pairs kernel
+(graphgan_amd/csrc/all_score.hip, all_score_reduce_bf16_x32_kernel), the tile-stream kernels of all_score.hip and topk_score.hip,
+the graph-softmax kernels -- fail the build if an instantiation uses scratch (csrc/check_no_scratch.sh) -- checked here on the
 auditor itself: the remarks of the current build pass, a copy with one spilled instantiation fails.  And the product path
 never touches the oracle."""
 import os
@@ -9,23 +10,36 @@ import subprocess
 import pytest
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graphgan_amd", "csrc")
-REMARKS = os.path.join(CSRC, "all_score.remarks")
 CHECK = os.path.join(CSRC, "check_no_scratch.sh")
+# object -> the audits of its Makefile rule: (kernel-name regex, min count, label)
+AUDITS = {
+    "all_score": [("all_score_reduce_bf16_x32_kernel", 10, "instantiations of the wide all-pairs kernel"),
+                  ("all_score_reduce_(f32|bf16)_kernel", 5, "all-pairs tile-stream kernels")],
+    "topk_score": [("topk_(f32|bf16)_kernel", 5, "top-K tile-stream kernels")],
+    "graph_softmax": [("gs_[a-z_]*kernel", 10, "graph-softmax kernels")],
+}
 
 
-@pytest.mark.skipif(not os.path.exists(REMARKS), reason="all_score.remarks is written by the build (make -C graphgan_amd/csrc)")
-def test_scratch_check_accepts_the_build_and_rejects_a_spill(tmp_path):
-    ok = subprocess.run(["bash", CHECK, REMARKS], capture_output=True, text=True)
+@pytest.mark.parametrize("obj", sorted(AUDITS))
+def test_scratch_check_accepts_the_build_and_rejects_a_spill(tmp_path, obj):
+    remarks = os.path.join(CSRC, obj + ".remarks")
+    if not os.path.exists(remarks):
+        pytest.skip("%s.remarks is written by the build (make -C graphgan_amd/csrc)" % obj)
+    args = [str(a) for audit in AUDITS[obj] for a in audit]
+    ok = subprocess.run(["bash", CHECK, remarks] + args, capture_output=True, text=True)
     assert ok.returncode == 0, ok.stderr
-    assert "no scratch, no spill" in ok.stdout
-    text = open(REMARKS).read()
-    m = re.search(r"(Function Name: _ZN2gg32all_score_reduce_bf16_x32_kernel.*?ScratchSize \[bytes/lane\]: )0", text, flags=re.S)
-    assert m
-    bad = text[:m.end() - 1] + "832" + text[m.end():]
-    p = tmp_path / "bad.remarks"
-    p.write_text(bad)
-    res = subprocess.run(["bash", CHECK, str(p)], capture_output=True, text=True)
-    assert res.returncode != 0 and "spills" in res.stderr
+    assert ok.stdout.count("no scratch, no spill") == len(AUDITS[obj])
+    for label in (a[2] for a in AUDITS[obj]):
+        assert label in ok.stdout
+    text = open(remarks).read()
+    for pat, _, _ in AUDITS[obj]:  # one instantiation of every audited kernel family spilled: rejected
+        m = re.search(r"(Function Name: \S*(?:%s)\S*.*?ScratchSize \[bytes/lane\]: )0" % pat, text, flags=re.S)
+        assert m
+        bad = text[:m.end() - 1] + "832" + text[m.end():]
+        p = tmp_path / "bad.remarks"
+        p.write_text(bad)
+        res = subprocess.run(["bash", CHECK, str(p)] + args, capture_output=True, text=True)
+        assert res.returncode != 0 and "spills" in res.stderr
 
 
 def test_product_path_never_touches_the_oracle():

@@ -68,7 +68,7 @@ def audit(path):
     print("%s" % os.path.relpath(path, ROOT))
     print("  %-78s %7s %6s %10s %9s %5s %8s %9s" % ("kernel", "instr", "loads", "load+wait0", "bpermute", "dpp", "scratch", "vmcnt(0)"))
     for r, n in zip(rows, names):
-        n = re.sub(r"\(.*", "", n).replace("void ", "").replace("gg::", "")
+        n = re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).replace("void ", "").replace("gg::", "")
         print("  %-78s %7d %6d %10d %9d %5d %8d %9d" % ((n[:78],) + r[1:]))
 
 
