@@ -115,6 +115,8 @@ SIGNATURES = {
     "gg_all_score_reduce": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]),
     "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
+    "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
+    "gg_prepare_pretrain": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _u64, _u32, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

@@ -62,3 +62,14 @@ engine_emb_sidecar = False    # also write <emb_filename>.bin: the same fp32 num
 engine_rec_ks = (2, 10, 20)   # app = "recommendation": the K of the P@K / R@K results line (each in [1, 256])
 engine_rec_precision = "fp32"  # app = "recommendation": ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
 engine_gen_nll = False        # evaluation(): append "gen_nll:NLL=<nll> reach=<reach> n=<n>" -- the held-out NLL of the generator's graph softmax
+# skip-gram pre-training from uniform random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
+# pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
+engine_pretrain = False
+engine_pretrain_walks = 10    # walks per start node and epoch
+engine_pretrain_len = 40      # nodes per walk
+engine_pretrain_window = 5
+engine_pretrain_neg = 5       # negatives per pair, drawn in proportion to round(16 * max(deg, 1) ^ 0.75)
+engine_pretrain_epochs = 1
+engine_pretrain_batch = 4096  # rows per optimizer step
+engine_pretrain_lr = 5e-3
+engine_pretrain_rows_per_call = 1 << 26  # rows one gg_prepare_pretrain call may produce (12 B each, device resident)

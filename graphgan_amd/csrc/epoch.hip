@@ -97,7 +97,10 @@ int gg_epoch_begin(gg_ctx *ctx, int32_t reset_d, int32_t reset_g) {
     GG_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_q3_store(ctx);
     if (rc != GG_OK) return rc;
-    if (reset_d) ctx->ep_rows = 0;
+    if (reset_d) {
+        ctx->ep_rows = 0;
+        ctx->ep_d_open = true;  // until gg_epoch_commit(1): gg_prepare_pretrain would replace the resident rows in between
+    }
     if (reset_g) ctx->ep_pairs = 0;
     return GG_OK;
 }
@@ -133,6 +136,7 @@ int gg_epoch_add(gg_ctx *ctx, const int32_t *roots, int32_t n_roots, int32_t do_
         // (no replica collective per batch: the ranks' batch counts differ; gg_epoch_commit exchanges the totals)
         ctx->in_epoch_add = true;
         if (do_d) {
+            ctx->ep_d_open = true;
             int64_t rows = 0;
             rc = gg_prepare_d(ctx, slots.data(), n_roots, seed, stream_d, &rows, nullptr);
             if (rc == GG_OK) rc = q3_copy(ctx, n_roots, /*to_store=*/true);
@@ -175,6 +179,7 @@ int gg_epoch_commit(gg_ctx *ctx, int32_t which, int64_t *n_out) {
         std::swap(ctx->d_label, ctx->ep_label);
         ctx->d_rows = rows;
         ctx->ep_rows = 0;
+        ctx->ep_d_open = false;
         rc = exchange_count_max(ctx, ctx->d_rows, &ctx->d_rows_max);
         if (rc != GG_OK) return rc;
         if (n_out) *n_out = rows;

@@ -523,13 +523,15 @@ int gg_destroy(gg_ctx *ctx) {
                       &ctx->x_recv_ids, &ctx->x_recv_rows, &ctx->x_nglob, &ctx->x_own, &ctx->st_item, &ctx->st_item2, &ctx->st_cur, &ctx->st_prev, &ctx->st_len,
                       &ctx->st_alive, &ctx->st_rank, &ctx->bfs_key, &ctx->bfs_bm, &ctx->bfs_misc, &ctx->bfs_sparse, &ctx->bfs_rowptr32, &ctx->lv_pfx, &ctx->dc_keys, &ctx->dc_vals, &ctx->dc_words, &ctx->lv_beg, &ctx->lv_k, &ctx->lv_chunks, &ctx->lv_coff, &ctx->lv_scores, &ctx->lv_chunk_owner, &ctx->lv_prefix, &ctx->lv_big, &ctx->lv_fe, &ctx->fin_list, &ctx->table_bad, &ctx->sgp_cnt, &ctx->sgp_off, &ctx->sgp_slot, &ctx->sgp_list, &ctx->sgp_tot, &ctx->sgp_key, &ctx->sgp_scan, &ctx->sgp_hub, &ctx->sg_hub, &ctx->hub_acc,
                       &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj,
-                      &ctx->gs_es, &ctx->gs_cpre};
+                      &ctx->gs_es, &ctx->gs_cpre, &ctx->pt_starts, &ctx->pt_paths, &ctx->pt_len, &ctx->pt_cnt, &ctx->pt_ptr, &ctx->pt_noise, &ctx->pt_sample};
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t e : ctx->lv_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &tr : ctx->tm_ev)
         for (hipEvent_t e : tr)
             if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->pt_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     for (hipEvent_t e : {ctx->ev_walk_done, ctx->ev_slots_done, ctx->ev_gen_pass, ctx->ev_main_mark, ctx->ev_fork, ctx->ev_join, ctx->ev_score[0], ctx->ev_score[1]})
         if (e) (void)hipEventDestroy(e);
@@ -572,6 +574,7 @@ int gg_set_graph_csr(gg_ctx *ctx, const int64_t *rowptr, const int32_t *col) {
     ctx->topk_adj.release();  // (the sorted copy of gg_topk_scores is rebuilt from the new lists on first use)
     ctx->topk_adj_valid = false;
     ctx->gs_es_valid = ctx->gs_cpre_valid = false;  // (gg_graph_softmax's edge scores are indexed by the edges of the graph)
+    ctx->pt_noise_set = false;  // (the pre-training noise weights were chosen for the old graph's degrees)
     GG_HIP(ctx, hipMalloc((void **)&ctx->g_rowptr, sizeof(int64_t) * (n + 1)));
     GG_HIP(ctx, hipMalloc((void **)&ctx->g_col, sizeof(int32_t) * (std::max<int64_t>(nnz, 1) + 4)));  // (+ 16 B: the BFS reads adjacency in 16-byte quads that may start at the last entry)
     GG_HIP(ctx, hipMemcpy(ctx->g_rowptr, rowptr, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));

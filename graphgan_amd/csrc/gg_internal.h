@@ -300,6 +300,16 @@ struct gg_ctx {
     int64_t gs_chunks = 0;
     bool gs_es_valid = false, gs_cpre_valid = false;
 
+    // skip-gram pre-training rows (pretrain.hip): walk buffers of their own -- the walk sampler's, the trees and the caches are not
+    // touched -- and the noise distribution: inclusive uint64 prefix sums of the caller's weights + the subsample the fill
+    // kernel keeps in LDS; dropped by gg_set_graph_csr
+    gg::DevBuf pt_starts, pt_paths, pt_len, pt_cnt, pt_ptr, pt_noise, pt_sample;
+    bool pt_noise_set = false;
+    uint64_t pt_noise_total = 0;
+    int32_t pt_sample_n = 0, pt_sample_stride = 1;
+    hipEvent_t pt_ev[4] = {};          // HIP events around pt_walk_kernel / pt_fill_kernel (profiling cadence 1)
+    bool ep_d_open = false;            // between gg_epoch_begin(reset_d) / a gg_epoch_add with do_d and gg_epoch_commit(1)
+
     std::string err;
 };
 

@@ -325,6 +325,54 @@ class Engine:
         slots = _i32(slots)
         self._ck(lib.gg_prepare_g_begin(self._ctx, _ptr(slots), len(slots), n_sample, seed, stream))
 
+    # ------------------------------------------------------------------ skip-gram pre-training rows
+    def pretrain_set_noise(self, weights=None):
+        """Noise distribution of the negatives of ``prepare_pretrain`` (gg_pretrain_set_noise): uint32 weights per node,
+        or None = uniform.  ``set_graph_csr`` drops it."""
+        if weights is None:
+            self._ck(lib.gg_pretrain_set_noise(self._ctx, None))
+            return
+        w = np.asarray(weights)
+        if w.shape != (self.n_node,) or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError("pretrain_set_noise: weights must be %d integers" % self.n_node)
+        if w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+            raise ValueError("pretrain_set_noise: weights must fit uint32")
+        if not w.any():
+            raise ValueError("pretrain_set_noise: every weight is zero")
+        w = np.ascontiguousarray(w, dtype=np.uint32)
+        self._ck(lib.gg_pretrain_set_noise(self._ctx, _ptr(w)))
+
+    def prepare_pretrain(self, starts, walks_per_start, walk_len, window, n_neg, seed, stream, fetch=False):
+        """Skip-gram rows from uniform random walks (gg_prepare_pretrain; contract P1-P5 in include/graphgan_hip.h):
+        ``walks_per_start`` walks of ``walk_len`` nodes from every node of ``starts``, window pairs as positives, ``n_neg``
+        negatives per pair.  The rows replace the resident discriminator rows (``get_d_data`` / ``d_pass``).  Returns the row
+        count, or with ``fetch`` (rows, paths int32 [walks, walk_len] with -1 behind a walk's end, path_len int32 [walks])."""
+        starts_a = np.asarray(starts)
+        if starts_a.ndim != 1 or (starts_a.size and not np.issubdtype(starts_a.dtype, np.integer)):
+            raise ValueError("prepare_pretrain: starts must be a 1-d array of integers")
+        if starts_a.size and (int(starts_a.min()) < 0 or int(starts_a.max()) >= self.n_node):
+            raise ValueError("prepare_pretrain: start outside [0, %d)" % self.n_node)
+        for name, val, lo, hi in (("walks_per_start", walks_per_start, 1, 2 ** 31 - 1), ("walk_len", walk_len, 1, 256),
+                                  ("window", window, 1, 16), ("n_neg", n_neg, 0, 64), ("seed", seed, 0, 2 ** 64 - 1),
+                                  ("stream", stream, 0, 2 ** 32 - 1)):
+            if isinstance(val, bool) or int(val) != val or not lo <= int(val) <= hi:
+                raise ValueError("prepare_pretrain: %s must be an integer in [%d, %d], got %r" % (name, lo, hi, val))
+        if self.n_node < 3:
+            raise ValueError("prepare_pretrain: needs at least 3 nodes")
+        starts_a = _i32(starts_a)
+        nw = len(starts_a) * int(walks_per_start)
+        if nw > 2 ** 31 - 1:
+            raise ValueError("prepare_pretrain: %d walks in one call" % nw)
+        paths = np.empty((nw, int(walk_len)), dtype=np.int32) if fetch else None
+        plen = np.empty(nw, dtype=np.int32) if fetch else None
+        n = ctypes.c_int64()
+        self._ck(lib.gg_prepare_pretrain(self._ctx, _ptr(starts_a), len(starts_a), int(walks_per_start), int(walk_len), int(window),
+                                         int(n_neg), int(seed), int(stream), ctypes.byref(n), _ptr(paths), _ptr(plen)))
+        self.d_rows = n.value
+        if not fetch:
+            return n.value
+        return n.value, paths, plen
+
     # ------------------------------------------------------------------ an epoch over root batches (trees not all resident)
     def epoch_begin(self, reset_d=True, reset_g=True):
         """Empty the accumulated discriminator rows / generator pairs of gg_epoch_add."""

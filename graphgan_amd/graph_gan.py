@@ -78,6 +78,14 @@ class GraphGAN(object):
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
         # reference never seeds it (Q5) -- seeding it here makes the whole run reproducible
         np.random.seed(self.seed)
+        # engine_pretrain: a missing pre-trained file is produced from the edge list (skip-gram on uniform random walks, on the
+        # device) and written in the reference's .emb text; the unchanged read below then finds it.  Off by default: a missing
+        # file raises as in the reference.  With replicas rank 0 writes, the others wait for the file.
+        if _cfg(cfg, "engine_pretrain", False):
+            from graphgan_amd import pretrain as _pretrain
+            if self.rank == 0:
+                _pretrain.ensure_pretrained(cfg, self.n_node, self._rowptr, self._col)
+            self.ctl.barrier()
         print("reading initial embeddings...")
         self.node_embed_init_d = utils.read_embeddings(filename=cfg.pretrain_emb_filename_d, n_node=self.n_node,
                                                        n_embed=cfg.n_emb)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GG_ABI_VERSION 9  /* gg_graph_softmax; 8: gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
+#define GG_ABI_VERSION 9  /* (gg_pretrain_set_noise / gg_prepare_pretrain are ADDITIVE: two new symbols, nothing existing changes, the number stays) gg_graph_softmax; 8: gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
 
 enum {
     GG_OK = 0,
@@ -357,6 +357,45 @@ int gg_graph_softmax(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t
                      float *logp /*[n_slots * n_node] or NULL*/,
                      const int64_t *q_off /*[n_slots + 1] or NULL*/, const int32_t *q_node, float *q_logp,
                      float *abort_mass /*[n_slots] or NULL*/, double *kernel_ms_out);
+
+/* ---- skip-gram pre-training rows (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour
+ * changes).  The reference starts from the pre_train .emb files of an external DeepWalk / node2vec run (config.py:33-34,
+ * utils.read_embeddings); these two calls produce, on the device, the rows that train such a table with the machinery that is
+ * already here: gg_d_pass on (center, neighbor, label) rows with sigmoid cross-entropy IS one-table skip-gram with negative
+ * sampling.  SAMPLING CONTRACT -- exact integer arithmetic throughout, so any decomposition over threads, calls or GPUs gives
+ * the same rows (the stance of S3-S5):
+ *   P1 uniform draw   m = uniform53(seed, stream, root = start node id, walk = w, hop): Philox4x32-10, counter (hop, w, start, stream),
+ *                     key seed (S4); t(K) = threshold(m, K) = floor(m * K / 2^53) (S5).
+ *   P2 walk           start node s, walk w in [0, walks_per_start): path[0] = s; for h = 1 .. walk_len - 1 with cur = path[h - 1],
+ *                     k = deg(cur): k == 0 ends the walk (path_len = h), else path[h] = col[rowptr[cur] + t(k)] drawn with hop = h.
+ *                     Walks are stored in the order (start index, w); entries behind path_len are -1.
+ *   P3 pairs          over the WHOLE path of length l (there is no back-step entry to drop, unlike get_node_pairs_from_path,
+ *                     graph_gan.py:272-291): for i ascending and j in [max(i - window, 0), min(i + window, l - 1)] ascending, j != i,
+ *                     pair number p is (path[i], path[j]).
+ *   P4 negatives      pair p, q in [0, n_neg): drawn with hop = walk_len + p * n_neg + q.  Noise distribution from the uint32
+ *                     weights of gg_pretrain_set_noise: C_j = inclusive prefix sums (uint64), W = C_{N-1} >= 1, node = the first j
+ *                     with C_j > t(W); without weights uniform: node = t(N).  While the node equals the pair's centre or its
+ *                     context: node = (node + 1) mod N (at most two steps; n_node >= 3 required).
+ *   P5 rows           walks in order, pairs in order; each pair gives (centre, context, 1.0) and then its n_neg rows
+ *                     (centre, neg_q, 0.0).  A walk of length l gives (1 + n_neg) * sum_i [min(i, window) + min(l - 1 - i, window)]
+ *                     rows, so row offsets are a scan over path_len.
+ *   limits            1 <= walk_len <= 256, 1 <= window <= 16, 0 <= n_neg <= 64, walks_per_start >= 1; repeated start nodes are
+ *                     allowed and give identical walks.
+ * gg_pretrain_set_noise: weight[n_node] (copied; all zero: GG_EINVAL) or NULL = uniform.  gg_set_graph_csr drops the table.
+ * gg_prepare_pretrain: needs gg_set_graph_csr.  REPLACES the resident discriminator rows exactly as a gg_prepare_d call does
+ * (gg_get_d_data and gg_d_pass then work on them unchanged); *n_rows_out = their number; paths [n_starts * walks_per_start *
+ * walk_len] and path_len [n_starts * walks_per_start] may be NULL.  It has path buffers of its own and neither reads nor writes
+ * the walk sampler's buffers, the trees, the edge-score / distribution caches or the generator: walks and graph-softmax results
+ * around it are unchanged and a gg_prepare_g_begin launch stays valid.  One host synchronisation (the row total); when even the
+ * bound (every walk at full length) exceeds 2^31 - 1 rows, a second one decides on the exact total.
+ * GG_EINVAL: no graph, a limit violated, a start out of range, an attached communicator (single rank only), a call between
+ * gg_epoch_begin(reset_d) / gg_epoch_add(do_d) and the matching gg_epoch_commit(1).  GG_ECAPACITY: more than 2^31 - 1 rows (or
+ * walks) in one call.  With profiling cadence 1 (gg_set_profiling) gg_counters.last_kernel_ms = HIP-event time of the row (fill)
+ * kernel and walk_kernel_ms / walk_launches also count this call's walk kernel. */
+int gg_pretrain_set_noise(gg_ctx *ctx, const uint32_t *weight /*[n_node] or NULL = uniform*/);
+int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, int32_t walks_per_start, int32_t walk_len,
+                        int32_t window, int32_t n_neg, uint64_t seed, uint32_t stream, int64_t *n_rows_out,
+                        int32_t *paths /*[n_starts*walks_per_start*walk_len] or NULL*/, int32_t *path_len /*or NULL*/);
 
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
