@@ -40,6 +40,7 @@ _base = os.environ.get("GRAPHGAN_ROOT", "../..")
 train_filename = _base + "/data/" + app + "/" + dataset + "_train.txt"
 test_filename = _base + "/data/" + app + "/" + dataset + "_test.txt"
 test_neg_filename = _base + "/data/" + app + "/" + dataset + "_test_neg.txt"
+labels_filename = _base + "/data/" + app + "/" + dataset + "_labels.txt"  # app = "node_classification": lines of "node label"
 pretrain_emb_filename_d = _base + "/pre_train/" + app + "/" + dataset + "_pre_train.emb"
 pretrain_emb_filename_g = _base + "/pre_train/" + app + "/" + dataset + "_pre_train.emb"
 emb_filenames = [_base + "/results/" + app + "/" + dataset + "_gen_.emb",
@@ -62,6 +63,12 @@ engine_emb_sidecar = False    # also write <emb_filename>.bin: the same fp32 num
 engine_rec_ks = (2, 10, 20)   # app = "recommendation": the K of the P@K / R@K results line (each in [1, 256])
 engine_rec_precision = "fp32"  # app = "recommendation": ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
 engine_gen_nll = False        # evaluation(): append "gen_nll:NLL=<nll> reach=<reach> n=<n>" -- the held-out NLL of the generator's graph softmax
+# app = "node_classification": softmax regression on the frozen embeddings, fitted on the device (gg_classifier_fit).  The split
+# seed is engine_seed.  The three fit defaults are provisional: they have not been measured on a labelled dataset.
+engine_nc_train_ratio = 0.9   # share of the labelled nodes that trains the classifier (the paper's 9:1 split)
+engine_nc_iters = 200         # full-batch Adam steps
+engine_nc_lr = 0.05
+engine_nc_l2 = 1e-4
 # skip-gram pre-training from uniform random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

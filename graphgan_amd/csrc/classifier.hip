@@ -1,0 +1,521 @@
+// classifier.hip -- node classification: multinomial logistic regression on rows of a resident table, gathered by node id.
+//     z = W . E[node] + b                         W fp32 [C, d], b fp32 [C]
+//     loss = -(1/M) sum log softmax(z)[label] + (l2 / 2) |W|^2            (the bias is not regularised)
+//     gW = (1/M) sum (p - onehot) E[node]^T + l2 W,   gb = (1/M) sum (p - onehot)
+// nc_sweep_kernel is the hot path: ONE sweep over the M rows gives the loss and both gradients.  A persistent workgroup (256
+// threads, 4 wavefronts) walks 64-row tiles; per tile
+//   1. the rows are gathered into LDS (Xs; the next tile's rows are already in flight to registers while this one computes),
+//   2. logits  Z[64, C] = Xs . W^T on v_mfma_f32_32x32x2_f32, W staged in LDS (Ws) once per workgroup -- in k-chunks per tile
+//      only where C x d does not fit beside the tile (C = 128 at d = 256),
+//   3. a max-subtracted softmax per row in LDS (4 threads per row), the row's loss term, P = p - onehot left in LDS (Ps),
+//   4. gradient  G[C, d] += P^T . Xs on the same matrix instruction, the accumulators in registers across all tiles of the
+//      workgroup; gb += column sums of Ps.
+// CT = ceil(C / 32) class tiles and DT = ceil(ld / 32) column tiles are template parameters: the accumulators are register
+// arrays with compile-time indices (an instantiation that spills fails the build, check_no_scratch.sh).
+// Determinism: the grid is min(NC_MAX_GRID, ceil(M / 64)) -- a function of M alone --, tiles go to workgroups round robin,
+// every workgroup writes its partial [C d + C + 1] to a stage and nc_reduce_kernel sums the stage in a fixed order.  No
+// floating-point atomics anywhere: two calls with the same inputs give the same bits.
+// nc_adam_kernel: full-batch Adam on (W, b); nc_predict_kernel: logits + argmax (ties to the lowest class).
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "gg_internal.h"
+
+namespace gg {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NC_RT = 64;           // rows per tile
+constexpr int NC_MAX_GRID = 512;    // workgroups of a sweep, at most
+constexpr int NC_MAX_C = 128, NC_MAX_D = 256;
+constexpr size_t NC_LDS = 150 * 1024;  // dynamic LDS of a sweep workgroup, at most
+constexpr int NC_RED_COLS = 32, NC_RED_SLICES = 8;  // nc_reduce_kernel: columns x stage slices per workgroup
+
+// C/D layout of v_mfma_f32_32x32x2_f32 (score_tiles.h, tile_row)
+__device__ __forceinline__ int nc_tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+struct SweepArgs {
+    const float *E;          // [n_node, ld]
+    const int32_t *nodes, *labels;
+    int64_t m;
+    int ld, d, C;
+    const float *W, *b;      // [C, d], [C]
+    int KW;                  // k-chunk of the W staging (>= ld: W is staged once)
+    float *part;             // [grid][C d + C + 1]
+};
+
+template <int CT, int DT>
+__global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
+    constexpr int XS = 32 * DT + 1, PS = 32 * CT + 1;       // row strides of Xs / Ps (odd: conflict-free column walks)
+    constexpr int N1 = (2 * CT + 3) / 4;                     // logit tiles (row half, class tile) per wavefront
+    constexpr int N2 = (CT * DT + 3) / 4;                    // gradient tiles (class tile, column tile) per wavefront
+    constexpr int NPF = 2 * DT;                              // float4 pieces of a tile per thread
+    extern __shared__ float nc_lds[];
+    __shared__ float bs[NC_MAX_C];  // the bias
+    __shared__ double red[256];  // the workgroup's loss terms (float64: a sum of M terms of size log C must keep the last digits)
+    float *Xs = nc_lds, *Ps = Xs + NC_RT * XS, *Ws = Ps + NC_RT * PS;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int ld = a.ld, d = a.d, C = a.C, KW = a.KW, WS = KW + 1;
+    const bool w_resident = KW >= ld;
+    const int64_t n_tiles = (a.m + NC_RT - 1) / NC_RT;
+
+    auto stage_w = [&](int k0) {
+        const int kw = min(KW, ld - k0);
+        for (int i = tid; i < 32 * CT * kw; i += 256) {
+            const int c = i / kw, kk = i - c * kw, k = k0 + kk;
+            Ws[c * WS + kk] = (c < C && k < d) ? a.W[(int64_t)c * d + k] : 0.f;
+        }
+    };
+    float4 pf[NPF];
+    auto fetch = [&](int64_t tile) {  // the tile's rows -> registers (rows behind M and columns behind ld: zeros)
+        const int64_t row0 = tile * NC_RT;
+#pragma unroll
+        for (int j = 0; j < NPF; ++j) {
+            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
+            pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tile < n_tiles && row0 + r < a.m && col < ld) pf[j] = *(const float4 *)(a.E + (int64_t)a.nodes[row0 + r] * ld + col);
+        }
+    };
+
+    f32x16 acc2[N2];
+#pragma unroll
+    for (int i = 0; i < N2; ++i)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc2[i][q] = 0.f;
+    double loss_acc = 0.0;
+    float gb_acc = 0.f;
+
+    if (tid < C) bs[tid] = a.b[tid];
+    if (w_resident) stage_w(0);
+    fetch(blockIdx.x);
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t row0 = tile * NC_RT;
+        __syncthreads();  // the previous tile's gradient product has read Xs / Ps
+#pragma unroll
+        for (int j = 0; j < NPF; ++j) {
+            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
+            float *x = Xs + r * XS + col;
+            x[0] = pf[j].x; x[1] = pf[j].y; x[2] = pf[j].z; x[3] = pf[j].w;
+        }
+        fetch(tile + gridDim.x);
+        if (w_resident) __syncthreads();
+
+        // 2. logits: unit u = wv + 4 i is (row half u & 1, class tile u >> 1)
+        f32x16 acc1[N1];
+#pragma unroll
+        for (int i = 0; i < N1; ++i)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc1[i][q] = 0.f;
+        for (int k0 = 0; k0 < ld; k0 += KW) {
+            if (!w_resident) {
+                __syncthreads();
+                stage_w(k0);
+                __syncthreads();
+            }
+            const int kmax = min(KW, ld - k0);
+#pragma unroll
+            for (int i = 0; i < N1; ++i) {
+                const int u = wv + 4 * i;
+                if (u < 2 * CT) {
+                    const float *xa = Xs + ((u & 1) * 32 + l31) * XS + k0 + half;
+                    const float *wb = Ws + ((u >> 1) * 32 + l31) * WS + half;
+                    int kk = 0;
+                    for (; kk + 16 <= kmax; kk += 16) {  // (8 steps: their 16 LDS reads are issued ahead of the matrix instructions)
+                        float xv[8], wv8[8];
+#pragma unroll
+                        for (int s = 0; s < 8; ++s) {
+                            xv[s] = xa[kk + 2 * s];
+                            wv8[s] = wb[kk + 2 * s];
+                        }
+#pragma unroll
+                        for (int s = 0; s < 8; ++s) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], wv8[s], acc1[i], 0, 0, 0);
+                    }
+                    for (; kk < kmax; kk += 2) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[kk], wb[kk], acc1[i], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N1; ++i) {
+            const int u = wv + 4 * i;
+            if (u < 2 * CT) {
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) Ps[((u & 1) * 32 + nc_tile_row(reg, half)) * PS + (u >> 1) * 32 + l31] = acc1[i][reg];
+            }
+        }
+        __syncthreads();
+
+        // 3. softmax of row tid >> 2 by 4 threads (classes q, q + 4, ...); P = p - onehot, zero for rows behind M and padded classes
+        {
+            const int r = tid >> 2, q = tid & 3;
+            const bool valid = row0 + r < a.m;
+            const int lab = valid ? a.labels[row0 + r] : -1;
+            float *p = Ps + r * PS;
+            float mx = -INFINITY, zl = 0.f;  // zl: the label's logit (held by the thread that owns the label's class)
+            for (int c = q; c < C; c += 4) {
+                const float z = p[c] + bs[c];
+                p[c] = z;
+                mx = fmaxf(mx, z);
+                zl = c == lab ? z : zl;
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 1));
+            mx = fmaxf(mx, __shfl_xor(mx, 2));
+            float s = 0.f;
+            for (int c = q; c < C; c += 4) {  // (one exponential per class: it is kept in place of the logit)
+                const float e = expf(p[c] - mx);
+                p[c] = e;
+                s += e;
+            }
+            s += __shfl_xor(s, 1);
+            s += __shfl_xor(s, 2);
+            const float inv = 1.f / s;
+            if (lab >= 0 && (lab & 3) == q) loss_acc += (double)((logf(s) + mx) - zl);
+            for (int c = q; c < C; c += 4) {
+                const float g = p[c] * inv - (c == lab ? 1.f : 0.f);
+                p[c] = valid ? g : 0.f;
+            }
+            for (int c = C + q; c < 32 * CT; c += 4) p[c] = 0.f;
+        }
+        __syncthreads();
+
+        // 4. gradient: tile t = wv + 4 i is (class tile t / DT, column tile t % DT); k runs over the 64 rows
+        if (tid < C) {
+#pragma unroll 8
+            for (int r = 0; r < NC_RT; ++r) gb_acc += Ps[r * PS + tid];
+        }
+#pragma unroll
+        for (int i = 0; i < N2; ++i) {
+            const int t = wv + 4 * i;
+            if (t < CT * DT) {
+                const float *pa = Ps + half * PS + (t / DT) * 32 + l31;
+                const float *xb = Xs + half * XS + (t % DT) * 32 + l31;
+#pragma unroll 8
+                for (int k = 0; k < NC_RT; k += 2) acc2[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[k * PS], xb[k * XS], acc2[i], 0, 0, 0);
+            }
+        }
+    }
+
+    // the workgroup's partial: gW [C, d], gb [C], loss
+    float *part = a.part + (int64_t)blockIdx.x * ((int64_t)C * d + C + 1);
+#pragma unroll
+    for (int i = 0; i < N2; ++i) {
+        const int t = wv + 4 * i;
+        if (t < CT * DT) {
+            const int col = (t % DT) * 32 + l31;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int c = (t / DT) * 32 + nc_tile_row(reg, half);
+                if (c < C && col < d) part[(int64_t)c * d + col] = acc2[i][reg];
+            }
+        }
+    }
+    if (tid < C) part[(int64_t)C * d + tid] = gb_acc;
+    red[tid] = loss_acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) part[(int64_t)C * d + C] = (float)red[0];
+}
+
+// grad[j] = (1/M) sum_g part[g][j] (+ l2 W[j] for j < C d) for the C d + C gradient entries: a workgroup takes NC_RED_COLS
+// entries, NC_RED_SLICES threads per entry sum contiguous slices of the stage, thread 0 of the entry adds the slices in order.
+// The LAST workgroup gives the loss: (1/M) sum_g part[g][C d + C] + (l2 / 2) |W|^2, both by strided sums and a fixed tree.
+__global__ __launch_bounds__(256) void nc_reduce_kernel(const float *part, int n_part, int C, int d, int64_t m, const float *W, float l2,
+                                                       float *grad, float *loss_out) {
+    __shared__ float sh[256];
+    __shared__ double shd[256];
+    const int tid = threadIdx.x;
+    const int64_t cd = (int64_t)C * d, n_out = cd + C, stride = n_out + 1;
+    const float fm = (float)m;
+    if (blockIdx.x == gridDim.x - 1) {
+        double sl = 0.0;  // (the loss terms in float64, as in the sweep)
+        float sw = 0.f;
+        for (int g = tid; g < n_part; g += 256) sl += (double)part[(int64_t)g * stride + n_out];
+        for (int64_t j = tid; j < cd; j += 256) sw += W[j] * W[j];
+        shd[tid] = sl;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (tid < w) shd[tid] += shd[tid + w];
+            __syncthreads();
+        }
+        const double tl = shd[0];
+        sh[tid] = sw;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (tid < w) sh[tid] += sh[tid + w];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const float loss = (float)(tl / (double)m + (double)(0.5f * l2 * sh[0]));
+            grad[n_out] = loss;
+            if (loss_out) *loss_out = loss;
+        }
+        return;
+    }
+    const int jc = tid % NC_RED_COLS, sl = tid / NC_RED_COLS;
+    const int64_t j = (int64_t)blockIdx.x * NC_RED_COLS + jc;
+    const int per = (n_part + NC_RED_SLICES - 1) / NC_RED_SLICES;
+    float s = 0.f;
+    if (j < n_out)
+        for (int g = sl * per; g < min(n_part, (sl + 1) * per); ++g) s += part[(int64_t)g * stride + j];
+    sh[tid] = s;
+    __syncthreads();
+    if (sl == 0 && j < n_out) {
+        float t = 0.f;
+        for (int q = 0; q < NC_RED_SLICES; ++q) t += sh[q * NC_RED_COLS + jc];
+        t /= fm;
+        if (j < cd) t += l2 * W[j];
+        grad[j] = t;
+    }
+}
+
+// full-batch Adam on theta = (W, b): c1 = 1 - beta1^t, c2 = 1 - beta2^t of step t (from 1)
+__global__ __launch_bounds__(256) void nc_adam_kernel(float *theta, float *mom, float *var, const float *grad, int64_t n, float lr, float c1, float c2) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float g = grad[j];
+    const float mj = 0.9f * mom[j] + (1.f - 0.9f) * g;
+    const float vj = 0.999f * var[j] + (1.f - 0.999f) * (g * g);
+    mom[j] = mj;
+    var[j] = vj;
+    theta[j] -= lr * (mj / c1) / (sqrtf(vj / c2) + 1e-8f);
+}
+
+// One wavefront per row at a time: W in LDS ([C][ld + 1], zero padded), the row in LDS, lane c (and c + 64) the class's dot
+// product; argmax over (logit descending, class ascending) by a butterfly.
+__global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld, int d, const int32_t *nodes, int64_t m, int C, const float *W,
+                                                        const float *b, int32_t *pred, float *logits) {
+    extern __shared__ float nc_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, WS = ld + 1;
+    float *Ws = nc_lds, *xs = Ws + C * WS + wv * ld;
+    for (int i = tid; i < C * ld; i += 256) {
+        const int c = i / ld, k = i - c * ld;
+        Ws[c * WS + k] = k < d ? W[(int64_t)c * d + k] : 0.f;
+    }
+    __syncthreads();
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < m; row += (int64_t)gridDim.x * 4) {
+        const float *x = E + (int64_t)nodes[row] * ld;
+        for (int k = lane; k < ld; k += 64) xs[k] = x[k];
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+        float best = -INFINITY;
+        int bc = 0x7fffffff;
+        for (int c = lane; c < C; c += 64) {
+            float z = 0.f;
+            const float *w = Ws + c * WS;
+            for (int k = 0; k < ld; ++k) z += w[k] * xs[k];
+            z += b[c];
+            if (logits) logits[row * C + c] = z;
+            if (z > best || bc == 0x7fffffff) {  // (the lane's classes ascend: a later equal logit does not replace)
+                best = z;
+                bc = c;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int oc = __shfl_xor(bc, o);
+            if (oc != 0x7fffffff && (bc == 0x7fffffff || ob > best || (ob == best && oc < bc))) {
+                best = ob;
+                bc = oc;
+            }
+        }
+        if (lane == 0) pred[row] = bc;
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+    }
+}
+
+typedef void (*SweepFn)(SweepArgs);
+#define NC_ROW(ct) {nc_sweep_kernel<ct, 1>, nc_sweep_kernel<ct, 2>, nc_sweep_kernel<ct, 3>, nc_sweep_kernel<ct, 4>, \
+                    nc_sweep_kernel<ct, 5>, nc_sweep_kernel<ct, 6>, nc_sweep_kernel<ct, 7>, nc_sweep_kernel<ct, 8>}
+const SweepFn nc_sweeps[4][8] = {NC_ROW(1), NC_ROW(2), NC_ROW(3), NC_ROW(4)};
+
+// The launch plan of a sweep: template instance, grid (a function of m alone), dynamic LDS and the W k-chunk.
+struct SweepPlan {
+    SweepFn fn;
+    int grid, KW;
+    size_t lds;
+};
+
+SweepPlan sweep_plan(int64_t m, int C, int ld) {
+    const int CT = cdiv(C, 32), DT = cdiv(ld, 32);
+    const size_t fixed = sizeof(float) * NC_RT * ((size_t)(32 * DT + 1) + (32 * CT + 1));
+    int KW = (int)((NC_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;
+    KW = KW >= ld ? ld : (KW / 4) * 4;
+    SweepPlan p;
+    p.fn = nc_sweeps[CT - 1][DT - 1];
+    p.grid = (int)std::min<int64_t>(NC_MAX_GRID, (m + NC_RT - 1) / NC_RT);
+    p.KW = KW;
+    p.lds = fixed + sizeof(float) * 32 * CT * (size_t)(KW + 1);
+    return p;
+}
+
+// device state of one call
+struct Fit {
+    DevBuf nodes, labels, theta, mom, var, grad, part, loss;
+    void release() { nodes.release(); labels.release(); theta.release(); mom.release(); var.release(); grad.release(); part.release(); loss.release(); }
+};
+
+int check_common(gg_ctx *ctx, const char *fn, int which, const int32_t *nodes, int64_t m, int n_class) {
+    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator), got %d", fn, which);
+    GG_CHECK(ctx, n_class >= 2 && n_class <= NC_MAX_C, GG_EINVAL, "%s: n_class = %d outside [2, %d]", fn, n_class, NC_MAX_C);
+    GG_CHECK(ctx, m >= 1 && m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld outside [1, 2^31 - 1]", fn, (long long)m);
+    GG_CHECK(ctx, ctx->n_emb <= NC_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, NC_MAX_D, ctx->n_emb);
+    GG_CHECK(ctx, nodes != nullptr, GG_EINVAL, "%s: nodes is NULL", fn);
+    for (int64_t i = 0; i < m; ++i)
+        GG_CHECK(ctx, nodes[i] >= 0 && nodes[i] < ctx->n_node, GG_EINVAL, "%s: node id %d (entry %lld) outside [0, %d)", fn, nodes[i], (long long)i, ctx->n_node);
+    return GG_OK;
+}
+
+int check_labels(gg_ctx *ctx, const char *fn, const int32_t *labels, int64_t m, int n_class) {
+    GG_CHECK(ctx, labels != nullptr, GG_EINVAL, "%s: labels is NULL", fn);
+    for (int64_t i = 0; i < m; ++i)
+        GG_CHECK(ctx, labels[i] >= 0 && labels[i] < n_class, GG_EINVAL, "%s: label %d (entry %lld) outside [0, n_class = %d)", fn, labels[i], (long long)i, n_class);
+    return GG_OK;
+}
+
+// nodes, labels, theta = (W, b) on the device; the stage and the gradient
+hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, const int32_t *nodes, const int32_t *labels, int64_t m, int C, const float *W, const float *b) {
+    const int d = ctx->n_emb;
+    const size_t cd = (size_t)C * d, n_par = cd + C;
+    hipError_t e = f.nodes.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = f.labels.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = f.theta.reserve(sizeof(float) * n_par);
+    if (e == hipSuccess) e = f.grad.reserve(sizeof(float) * (n_par + 1));
+    if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (n_par + 1) * p.grid);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.labels.p, labels, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && p.lds > 48 * 1024) e = hipFuncSetAttribute((const void *)p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    return e;
+}
+
+// sweep + reduce of theta on ctx->stream: grad [C d + C + 1] (the loss last), the loss also to *loss_dev
+void enqueue_lossgrad(gg_ctx *ctx, const Fit &f, const SweepPlan &p, int which, int64_t m, int C, float l2, float *loss_dev) {
+    const int d = ctx->n_emb;
+    const int64_t cd = (int64_t)C * d;
+    SweepArgs a{ctx->model[which].E, f.nodes.as<int32_t>(), f.labels.as<int32_t>(), m, ctx->ld, d, C, f.theta.as<float>(), f.theta.as<float>() + cd, p.KW, f.part.as<float>()};
+    hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(256), p.lds, ctx->stream, a);
+    hipLaunchKernelGGL(nc_reduce_kernel, dim3(cdiv(cd + C, NC_RED_COLS) + 1), dim3(256), 0, ctx->stream, f.part.as<float>(), p.grid, C, d, m,
+                       f.theta.as<float>(), l2, f.grad.as<float>(), loss_dev);
+}
+
+}  // namespace
+
+}  // namespace gg
+
+using namespace gg;
+
+// gg_classifier_lossgrad: see include/graphgan_hip.h.
+extern "C" int gg_classifier_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, const float *W,
+                                      const float *b, float l2, float *loss_out, float *gW_out, float *gb_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_common(ctx, "gg_classifier_lossgrad", which, nodes, m, n_class)) return rc;
+    if (const int rc = check_labels(ctx, "gg_classifier_lossgrad", labels, m, n_class)) return rc;
+    GG_CHECK(ctx, W && b && loss_out && gW_out && gb_out, GG_EINVAL, "gg_classifier_lossgrad: W, b, loss_out, gW_out, gb_out must not be NULL");
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "gg_classifier_lossgrad: l2 must be finite and >= 0");
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int C = n_class;
+    const size_t cd = (size_t)C * ctx->n_emb;
+    const SweepPlan p = sweep_plan(m, C, ctx->ld);
+    Fit f;
+    hipError_t e = fit_upload(ctx, f, p, nodes, labels, m, C, W, b);
+    if (e == hipSuccess) {
+        enqueue_lossgrad(ctx, f, p, which, m, C, l2, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(gW_out, f.grad.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(gb_out, f.grad.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    f.release();
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_lossgrad: %s", hipGetErrorString(e));
+    return GG_OK;
+}
+
+// gg_classifier_fit: see include/graphgan_hip.h.
+extern "C" int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, int iters, float lr,
+                                 float l2, float *W_inout, float *b_inout, float *loss_out, double *ms_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_common(ctx, "gg_classifier_fit", which, nodes, m, n_class)) return rc;
+    if (const int rc = check_labels(ctx, "gg_classifier_fit", labels, m, n_class)) return rc;
+    GG_CHECK(ctx, W_inout && b_inout, GG_EINVAL, "gg_classifier_fit: W_inout and b_inout must not be NULL");
+    GG_CHECK(ctx, iters >= 1 && iters <= 1000000, GG_EINVAL, "gg_classifier_fit: iters = %d outside [1, 1000000]", iters);
+    GG_CHECK(ctx, lr > 0.f && std::isfinite(lr), GG_EINVAL, "gg_classifier_fit: lr must be finite and > 0");
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "gg_classifier_fit: l2 must be finite and >= 0");
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int C = n_class;
+    const size_t cd = (size_t)C * ctx->n_emb, n_par = cd + C;
+    const SweepPlan p = sweep_plan(m, C, ctx->ld);
+    Fit f;
+    hipError_t e = fit_upload(ctx, f, p, nodes, labels, m, C, W_inout, b_inout);
+    if (e == hipSuccess) e = f.mom.reserve(sizeof(float) * n_par);
+    if (e == hipSuccess) e = f.var.reserve(sizeof(float) * n_par);
+    if (e == hipSuccess) e = f.loss.reserve(sizeof(float) * iters);
+    if (e == hipSuccess) e = hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream);
+    if (e == hipSuccess) {
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        double b1p = 1.0, b2p = 1.0;
+        for (int t = 0; t < iters; ++t) {
+            b1p *= 0.9;
+            b2p *= 0.999;
+            enqueue_lossgrad(ctx, f, p, which, m, C, l2, f.loss.as<float>() + t);
+            hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
+                               f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
+        }
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(W_inout, f.theta.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b_inout, f.theta.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && loss_out) e = hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    float ms = 0.f;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    f.release();
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_fit: %s", hipGetErrorString(e));
+    if (ms_out) *ms_out = ms;
+    return GG_OK;
+}
+
+// gg_classifier_predict: see include/graphgan_hip.h.
+extern "C" int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
+                                     int32_t *pred_out, float *logits_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_common(ctx, "gg_classifier_predict", which, nodes, m, n_class)) return rc;
+    GG_CHECK(ctx, W && b && pred_out, GG_EINVAL, "gg_classifier_predict: W, b and pred_out must not be NULL");
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int C = n_class, d = ctx->n_emb, ld = ctx->ld;
+    const size_t cd = (size_t)C * d;
+    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld);
+    DevBuf d_nodes, d_theta, d_pred, d_logits;
+    auto rel = [&]() { d_nodes.release(); d_theta.release(); d_pred.release(); d_logits.release(); };
+    hipError_t e = d_nodes.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = d_theta.reserve(sizeof(float) * (cd + C));
+    if (e == hipSuccess) e = d_pred.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess && logits_out) e = d_logits.reserve(sizeof(float) * (size_t)m * C);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute((const void *)nc_predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+        const int grid = (int)std::min<int64_t>(1024, (m + 3) / 4);
+        hipLaunchKernelGGL(nc_predict_kernel, dim3(grid), dim3(256), lds, ctx->stream, ctx->model[which].E, ld, d, d_nodes.as<int32_t>(), m, C,
+                           d_theta.as<float>(), d_theta.as<float>() + cd, d_pred.as<int32_t>(), logits_out ? d_logits.as<float>() : nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(pred_out, d_pred.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && logits_out) e = hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m * C, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    rel();
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_predict: %s", hipGetErrorString(e));
+    return GG_OK;
+}

@@ -550,6 +550,82 @@ class Engine:
             return [q[off[k]:off[k + 1]] for k in range(ns)], abort
         return q, abort
 
+    # ------------------------------------------------------------------ node classification (gg_classifier_*)
+    def _nc_args(self, fn, nodes, which, n_class, labels=None):
+        if which not in (0, 1):
+            raise ValueError("%s: which must be 0 (generator) or 1 (discriminator), got %r" % (fn, which))
+        if isinstance(n_class, bool) or int(n_class) != n_class or not 2 <= int(n_class) <= 128:
+            raise ValueError("%s: n_class must be an integer in [2, 128], got %r" % (fn, n_class))
+        nodes_a = np.asarray(nodes)
+        if nodes_a.ndim != 1 or nodes_a.size == 0 or not np.issubdtype(nodes_a.dtype, np.integer):
+            raise ValueError("%s: nodes must be a non-empty 1-d array of integers" % fn)
+        if int(nodes_a.min()) < 0 or int(nodes_a.max()) >= self.n_node:
+            raise ValueError("%s: node id outside [0, %d)" % (fn, self.n_node))
+        if labels is None:
+            return _i32(nodes_a), None
+        labels_a = np.asarray(labels)
+        if labels_a.shape != nodes_a.shape or not np.issubdtype(labels_a.dtype, np.integer):
+            raise ValueError("%s: labels must be integers, one per node" % fn)
+        if int(labels_a.min()) < 0 or int(labels_a.max()) >= int(n_class):
+            raise ValueError("%s: label outside [0, n_class = %d)" % (fn, int(n_class)))
+        return _i32(nodes_a), _i32(labels_a)
+
+    def _nc_params(self, fn, W, b):
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if W.ndim != 2 or W.shape[1] != self.n_emb or b.shape != (W.shape[0],):
+            raise ValueError("%s: W must be [n_class, %d] and b [n_class], got %r and %r" % (fn, self.n_emb, W.shape, b.shape))
+        return W, b
+
+    def classifier_lossgrad(self, nodes, labels, W, b, which=0, l2=0.0):
+        """Loss and gradients of multinomial logistic regression on the rows ``nodes`` of table ``which`` (0 = gen, 1 = dis)
+        at (W [C, n_emb], b [C]) (gg_classifier_lossgrad: one fused sweep on the device).  Returns dict(loss, gW, gb)."""
+        W, b = self._nc_params("classifier_lossgrad", W, b)
+        C = int(W.shape[0])
+        nodes_a, labels_a = self._nc_args("classifier_lossgrad", nodes, which, C, labels)
+        loss = np.zeros(1, dtype=np.float32)
+        gW = np.empty_like(W)
+        gb = np.empty_like(b)
+        self._ck(lib.gg_classifier_lossgrad(self._ctx, which, _ptr(nodes_a), _ptr(labels_a), len(nodes_a), C, _ptr(W), _ptr(b), float(l2),
+                                            _ptr(loss), _ptr(gW), _ptr(gb)))
+        return dict(loss=float(loss[0]), gW=gW, gb=gb)
+
+    def classifier_fit(self, nodes, labels, n_class, which=0, iters=200, lr=0.05, l2=1e-4, W=None, b=None):
+        """``iters`` steps of full-batch Adam on the logistic-regression loss of the rows ``nodes`` of table ``which``
+        (gg_classifier_fit), from zeros unless (W, b) are given; fit on the device, one synchronisation.  Returns
+        dict(W fp32 [n_class, n_emb], b fp32 [n_class], loss fp32 [iters] -- the loss before each update --, ms)."""
+        nodes_a, labels_a = self._nc_args("classifier_fit", nodes, which, n_class, labels)
+        C = int(n_class)
+        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
+            raise ValueError("classifier_fit: iters must be an integer >= 1, got %r" % (iters,))
+        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
+            raise ValueError("classifier_fit: lr must be > 0 and l2 >= 0, got %r and %r" % (lr, l2))
+        if (W is None) != (b is None):
+            raise ValueError("classifier_fit: give both W and b, or neither")
+        if W is None:
+            W, b = np.zeros((C, self.n_emb), dtype=np.float32), np.zeros(C, dtype=np.float32)
+        else:
+            W, b = self._nc_params("classifier_fit", W, b)
+            if W.shape[0] != C:
+                raise ValueError("classifier_fit: W has %d rows, n_class is %d" % (W.shape[0], C))
+            W, b = W.copy(), b.copy()
+        loss = np.empty(int(iters), dtype=np.float32)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_classifier_fit(self._ctx, which, _ptr(nodes_a), _ptr(labels_a), len(nodes_a), C, int(iters), float(lr), float(l2),
+                                       _ptr(W), _ptr(b), _ptr(loss), ctypes.byref(ms)))
+        return dict(W=W, b=b, loss=loss, ms=ms.value)
+
+    def classifier_predict(self, nodes, W, b, which=0, logits=False):
+        """argmax_c (W . E[node] + b)[c] of the rows ``nodes`` of table ``which``, ties to the lowest class
+        (gg_classifier_predict).  Returns pred int32 [len(nodes)], or (pred, logits fp32 [len(nodes), C]) with ``logits``."""
+        W, b = self._nc_params("classifier_predict", W, b)
+        C = int(W.shape[0])
+        nodes_a, _ = self._nc_args("classifier_predict", nodes, which, C)
+        pred = np.empty(len(nodes_a), dtype=np.int32)
+        z = np.empty((len(nodes_a), C), dtype=np.float32) if logits else None
+        self._ck(lib.gg_classifier_predict(self._ctx, which, _ptr(nodes_a), len(nodes_a), C, _ptr(W), _ptr(b), _ptr(pred), _ptr(z)))
+        return (pred, z) if logits else pred
+
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""
         out = np.zeros((self.n_node, self.n_emb), dtype=np.float32)

@@ -45,6 +45,7 @@ from graphgan_amd import _lib, engine as _engine, parallel, utils  # noqa: E402
 from graphgan_amd.evaluation import link_prediction as lp  # noqa: E402
 from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
+from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -53,13 +54,23 @@ def _cfg(cfg, name, default):
     return getattr(cfg, name, default)
 
 
+def _check_gen_nll(cfg):
+    """app = "node_classification" runs without test edges; the held-out NLL line does not (checked before anything is computed)"""
+    if cfg.app == "node_classification" and _cfg(cfg, "engine_gen_nll", False) and not os.path.isfile(cfg.test_filename):
+        raise ValueError("engine_gen_nll needs test edges: config.test_filename does not exist under app = 'node_classification'")
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
         cfg = self.config
         print("reading graphs...")
         # native ingest (same adjacency as utils.read_edges, utils.py:12-47); self.graph[i] still lists i's neighbours
-        self.n_node, self._rowptr, self._col = _engine.read_edges_csr(cfg.train_filename, cfg.test_filename)
+        _check_gen_nll(cfg)
+        test_filename = cfg.test_filename
+        if cfg.app == "node_classification" and not os.path.isfile(test_filename):
+            test_filename = ""  # the app has no test edges
+        self.n_node, self._rowptr, self._col = _engine.read_edges_csr(cfg.train_filename, test_filename)
         self.graph = _engine.CSRGraph(self._rowptr, self._col)
         # One process per GPU (torch.distributed.run exports RANK / WORLD_SIZE / LOCAL_RANK; a plain `python graph_gan.py`
         # is world 1).  The reference is a single tf.Session (:57-61): every rank here holds full replicas of both models,
@@ -430,6 +441,7 @@ class GraphGAN(object):
     @staticmethod
     def evaluation(self):
         cfg = self.config
+        _check_gen_nll(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -446,6 +458,17 @@ class GraphGAN(object):
                 re_ = rec.RecommendEval(cfg.emb_filenames[i], cfg.train_filename, cfg.test_filename, self.n_node, cfg.n_emb,
                                         engine=self.engine, which=i, ks=ks, precision=_cfg(cfg, "engine_rec_precision", "fp32"))
                 results.append(rec.format_results(cfg.modes[i], re_.eval_recommendation(), ks))
+        elif cfg.app == "node_classification":
+            # accuracy / Macro-F1 of softmax regression on the frozen rows, fitted and applied on the device (gg_classifier_*); one
+            # line per mode: "gen:acc=<a> macro_f1=<f> n_train=<n> n_test=<n>"
+            if not hasattr(cfg, "labels_filename"):
+                raise ValueError("app = 'node_classification' needs config.labels_filename (lines of 'node label')")
+            for i in range(2):
+                nce = nc.NodeClassifyEval(cfg.emb_filenames[i], cfg.labels_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i,
+                                          train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed,
+                                          iters=int(_cfg(cfg, "engine_nc_iters", 200)), lr=float(_cfg(cfg, "engine_nc_lr", 0.05)),
+                                          l2=float(_cfg(cfg, "engine_nc_l2", 1e-4)))
+                results.append(nc.format_results(cfg.modes[i], nce.eval_node_classification()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

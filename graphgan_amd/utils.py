@@ -31,6 +31,30 @@ def read_edges(train_filename, test_filename):
     return len(graph), graph
 
 
+def read_labels(filename, n_node):
+    """Lines of ``node<whitespace>label`` (integer labels of any value, one label per node; blank lines are skipped)
+    -> (nodes int64 sorted, classes int64 in [0, C), label_values int64 [C] sorted): ``classes[i]`` is the rank of the label of
+    ``nodes[i]`` among the distinct label values.  A node listed twice or an id outside [0, n_node) raises ValueError."""
+    seen = {}
+    with open(filename, "r") as f:
+        for no, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) != 2:
+                raise ValueError("%s:%d: expected 'node label', got %r" % (filename, no, line.strip()))
+            node, label = int(tok[0]), int(tok[1])
+            if not 0 <= node < n_node:
+                raise ValueError("%s:%d: node id %d outside [0, %d)" % (filename, no, node, n_node))
+            if node in seen:
+                raise ValueError("%s:%d: node %d is listed twice (one label per node)" % (filename, no, node))
+            seen[node] = label
+    nodes = np.array(sorted(seen), dtype=np.int64)
+    labels = np.array([seen[int(v)] for v in nodes], dtype=np.int64)
+    values, classes = np.unique(labels, return_inverse=True)
+    return nodes, classes.astype(np.int64).reshape(-1), values.astype(np.int64)
+
+
 def read_embeddings(filename, n_node, n_embed):
     """``.emb`` text -> float64 [n_node, n_embed]; the first line is a header; rows whose id is
     absent keep uniform [0, 1) draws from the global numpy RNG (utils.py:57-67)."""

@@ -397,6 +397,34 @@ int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, in
                         int32_t window, int32_t n_neg, uint64_t seed, uint32_t stream, int64_t *n_rows_out,
                         int32_t *paths /*[n_starts*walks_per_start*walk_len] or NULL*/, int32_t *path_len /*or NULL*/);
 
+/* ---- node classification (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * The GraphGAN paper's third application: multinomial logistic regression on the FROZEN rows of table `which` (0 = generator,
+ * 1 = discriminator), gathered by node id from the resident table -- nothing of size m x n_emb crosses to the host.  With
+ * C = n_class, d = n_emb, W fp32 [C, d] row-major, b fp32 [C], rows i = 0 .. m - 1 (nodes[i], labels[i]):
+ *   z_i  = W . E[nodes[i]] + b,   p_i = softmax(z_i) (max-subtracted)
+ *   loss = -(1/m) sum_i log p_i[labels[i]] + (l2 / 2) |W|^2                  (the bias is not regularised)
+ *   gW   = (1/m) sum_i (p_i - onehot(labels[i])) E[nodes[i]]^T + l2 W,   gb = (1/m) sum_i (p_i - onehot(labels[i]))
+ * gg_classifier_lossgrad: loss_out[1], gW_out[C * d], gb_out[C] at the given (W, b): ONE fused sweep (every row is read once;
+ *   both products on v_mfma_f32_32x32x2_f32, fp32 throughout) and a reduction.
+ * gg_classifier_fit: `iters` steps of full-batch Adam (beta1 = 0.9, beta2 = 0.999, eps = 1e-8, bias-corrected, step count from
+ *   1: m_t = b1 m + (1 - b1) g, v_t = b2 v + (1 - b2) g^2, theta -= lr (m_t / (1 - b1^t)) / (sqrt(v_t / (1 - b2^t)) + eps)) on
+ *   (W, b) from the values in W_inout / b_inout, which receive the result.  loss_out[t] (may be NULL) is the loss at the
+ *   parameters BEFORE update t.  All iterations are enqueued on the engine's stream behind one another; one synchronisation
+ *   at the end.  ms_out (may be NULL): HIP-event time of the iterations.
+ * gg_classifier_predict: pred_out[i] = argmax_c z_i[c], ties to the LOWEST class; logits_out (may be NULL) [m, C] row-major.
+ * limits       2 <= n_class <= 128, n_emb <= 256, 1 <= m <= 2^31 - 1, labels in [0, n_class), node ids in [0, n_node) and
+ *              free to repeat; a class without a row is legal; iters >= 1, lr > 0, l2 >= 0.  Anything else: GG_EINVAL, the
+ *              gg_last_error text names the limit, nothing is launched.
+ * determinism  the rows are split over a grid that depends on m alone (not on the device), every workgroup writes its
+ *              partial sums to a stage, a second kernel adds the stage in a fixed order; there are no floating-point
+ *              atomics: two calls with the same inputs and table give the same bits. */
+int gg_classifier_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class,
+                           const float *W, const float *b, float l2, float *loss_out, float *gW_out, float *gb_out);
+int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class,
+                      int iters, float lr, float l2, float *W_inout, float *b_inout, float *loss_out /* [iters] or NULL */, double *ms_out);
+int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
+                          int32_t *pred_out, float *logits_out /* NULL or [m, n_class] */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
