@@ -69,6 +69,12 @@ engine_nc_train_ratio = 0.9   # share of the labelled nodes that trains the clas
 engine_nc_iters = 200         # full-batch Adam steps
 engine_nc_lr = 0.05
 engine_nc_l2 = 1e-4
+# multi-label files (BlogCatalog, Wikipedia: lines of "node label [label ...]", utils.read_multilabels): one-vs-rest logistic
+# regression on the device (gg_classifier_ml_fit) and the line "acc= micro_f1= macro_f1= n_train= n_test=".  Protocol "topk"
+# predicts for a test node as many labels as it truly has (the customary protocol: it reads the test nodes' label COUNTS),
+# "threshold" the classes with a positive logit.
+engine_nc_multilabel = False
+engine_nc_ml_protocol = "topk"
 # skip-gram pre-training from uniform random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

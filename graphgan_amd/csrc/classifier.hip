@@ -16,6 +16,15 @@
 // every workgroup writes its partial [C d + C + 1] to a stage and nc_reduce_kernel sums the stage in a fixed order.  No
 // floating-point atomics anywhere: two calls with the same inputs give the same bits.
 // nc_adam_kernel: full-batch Adam on (W, b); nc_predict_kernel: logits + argmax (ties to the lowest class).
+//
+// Multi-label (gg_classifier_ml_*): one-vs-rest logistic regression against a multi-hot mask uint32 [M][CT] (bit c & 31 of word
+// c >> 5 = row has class c):
+//     loss = (1/M) sum_i sum_c [softplus(z_ic) - y_ic z_ic] + (l2 / 2) |W|^2,   gW = (1/M) sum (sigmoid(z) - y) E[node]^T + l2 W
+// It is the SAME sweep with a second compile-time variant of step 3 (template parameter ML; steps 1, 2, 4, the epilogue, the
+// stage, nc_reduce_kernel and nc_adam_kernel are shared): per class, with e = exp(-|z|), softplus(z) = max(z, 0) + log1p(e) and
+// sigmoid(z) = (z >= 0 ? 1 : e) / (1 + e) -- finite at any logit, and exactly 0 or 1 once e underflows.
+// nc_ml_predict_kernel: logits, the rank of every class in (logit descending, class ascending) and the mask of the first k[i]
+// classes of that order (or of the classes with z > 0).
 #include <math.h>
 
 #include <algorithm>
@@ -40,15 +49,16 @@ __device__ __forceinline__ int nc_tile_row(int reg, int half) { return (reg & 3)
 
 struct SweepArgs {
     const float *E;          // [n_node, ld]
-    const int32_t *nodes, *labels;
+    const int32_t *nodes, *labels;  // labels: one class per row (softmax variant)
     int64_t m;
     int ld, d, C;
     const float *W, *b;      // [C, d], [C]
     int KW;                  // k-chunk of the W staging (>= ld: W is staged once)
     float *part;             // [grid][C d + C + 1]
+    const uint32_t *bits;    // [m][CT] multi-hot label mask (sigmoid variant)
 };
 
-template <int CT, int DT>
+template <int CT, int DT, bool ML>
 __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
     constexpr int XS = 32 * DT + 1, PS = 32 * CT + 1;       // row strides of Xs / Ps (odd: conflict-free column walks)
     constexpr int N1 = (2 * CT + 3) / 4;                     // logit tiles (row half, class tile) per wavefront
@@ -148,8 +158,29 @@ __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
         }
         __syncthreads();
 
-        // 3. softmax of row tid >> 2 by 4 threads (classes q, q + 4, ...); P = p - onehot, zero for rows behind M and padded classes
-        {
+        // 3. the per-row loss stage of row tid >> 2 by 4 threads (classes q, q + 4, ...); P is zero for rows behind M and padded classes
+        if constexpr (ML) {
+            // per-class sigmoid cross-entropy against the row's mask words (word j holds classes 32 j .. 32 j + 31; CT words per
+            // row); P = sigmoid(z) - y.  No row maximum, nothing crosses lanes.
+            const int r = tid >> 2, q = tid & 3;
+            const bool valid = row0 + r < a.m;
+            float *p = Ps + r * PS;
+#pragma unroll
+            for (int j = 0; j < CT; ++j) {
+                const uint32_t yw = valid ? a.bits[(row0 + r) * CT + j] : 0u;
+                const int c_end = min(C, 32 * j + 32);
+                for (int c = 32 * j + q; c < c_end; c += 4) {
+                    const float z = p[c] + bs[c];
+                    const bool y = (yw >> (c & 31)) & 1u;
+                    const float e = expf(-fabsf(z));
+                    const float sg = (z >= 0.f ? 1.f : e) / (1.f + e);
+                    if (valid) loss_acc += (double)(fmaxf(z, 0.f) + log1pf(e)) - (y ? (double)z : 0.0);
+                    p[c] = valid ? sg - (y ? 1.f : 0.f) : 0.f;
+                }
+            }
+            for (int c = C + q; c < 32 * CT; c += 4) p[c] = 0.f;
+        } else {
+            // max-subtracted softmax; P = p - onehot
             const int r = tid >> 2, q = tid & 3;
             const bool valid = row0 + r < a.m;
             const int lab = valid ? a.labels[row0 + r] : -1;
@@ -286,6 +317,64 @@ __global__ __launch_bounds__(256) void nc_adam_kernel(float *theta, float *mom, 
     theta[j] -= lr * (mj / c1) / (sqrtf(vj / c2) + 1e-8f);
 }
 
+// nc_ml_predict_kernel -- one wavefront per row at a time, W and the row in LDS as in nc_predict_kernel below.  Lane c holds
+// the logits of classes c and c + 64 and publishes them to LDS (zs); every lane then counts, over all C published logits (one
+// broadcast read each), the classes that come before its own in the total order (logit descending, class ascending): the rank.
+// A class is selected when rank < k[row] (k given) or z > 0 (k NULL).  Two ballots give the four mask words; lane j stores word j.
+__global__ __launch_bounds__(256) void nc_ml_predict_kernel(const float *E, int ld, int d, const int32_t *nodes, int64_t m, int C, const float *W,
+                                                           const float *b, const int32_t *k, uint32_t *pred_bits, float *logits) {
+    extern __shared__ float nc_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, WS = ld + 1, CW = (C + 31) >> 5;
+    float *Ws = nc_lds, *xs = Ws + C * WS + wv * ld, *zs = Ws + C * WS + 4 * ld + wv * NC_MAX_C;
+    for (int i = tid; i < C * ld; i += 256) {
+        const int c = i / ld, kk = i - c * ld;
+        Ws[c * WS + kk] = kk < d ? W[(int64_t)c * d + kk] : 0.f;
+    }
+    __syncthreads();
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < m; row += (int64_t)gridDim.x * 4) {
+        const float *x = E + (int64_t)nodes[row] * ld;
+        for (int kk = lane; kk < ld; kk += 64) xs[kk] = x[kk];
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+        float z0 = 0.f, z1 = 0.f;
+        if (lane < C) {
+            const float *w = Ws + lane * WS;
+            for (int kk = 0; kk < ld; ++kk) z0 += w[kk] * xs[kk];
+            z0 += b[lane];
+            if (logits) logits[row * C + lane] = z0;
+            zs[lane] = z0;
+        }
+        if (lane + 64 < C) {
+            const float *w = Ws + (lane + 64) * WS;
+            for (int kk = 0; kk < ld; ++kk) z1 += w[kk] * xs[kk];
+            z1 += b[lane + 64];
+            if (logits) logits[row * C + lane + 64] = z1;
+            zs[lane + 64] = z1;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+        bool sel0, sel1;
+        if (k) {
+            int rank0 = 0, rank1 = 0;
+            for (int c = 0; c < C; ++c) {
+                const float o = zs[c];
+                rank0 += (o > z0 || (o == z0 && c < lane)) ? 1 : 0;
+                rank1 += (o > z1 || (o == z1 && c < lane + 64)) ? 1 : 0;
+            }
+            const int kr = k[row];
+            sel0 = lane < C && rank0 < kr;
+            sel1 = lane + 64 < C && rank1 < kr;
+        } else {
+            sel0 = lane < C && z0 > 0.f;
+            sel1 = lane + 64 < C && z1 > 0.f;
+        }
+        const unsigned long long m0 = __ballot(sel0), m1 = __ballot(sel1);  // classes 0 .. 63, 64 .. 127
+        if (lane < CW) pred_bits[row * CW + lane] = (uint32_t)((lane < 2 ? m0 : m1) >> (32 * (lane & 1)));
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+    }
+}
+
 // One wavefront per row at a time: W in LDS ([C][ld + 1], zero padded), the row in LDS, lane c (and c + 64) the class's dot
 // product; argmax over (logit descending, class ascending) by a butterfly.
 __global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld, int d, const int32_t *nodes, int64_t m, int C, const float *W,
@@ -332,9 +421,11 @@ __global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld,
 }
 
 typedef void (*SweepFn)(SweepArgs);
-#define NC_ROW(ct) {nc_sweep_kernel<ct, 1>, nc_sweep_kernel<ct, 2>, nc_sweep_kernel<ct, 3>, nc_sweep_kernel<ct, 4>, \
-                    nc_sweep_kernel<ct, 5>, nc_sweep_kernel<ct, 6>, nc_sweep_kernel<ct, 7>, nc_sweep_kernel<ct, 8>}
-const SweepFn nc_sweeps[4][8] = {NC_ROW(1), NC_ROW(2), NC_ROW(3), NC_ROW(4)};
+#define NC_ROW(ct, ml) {nc_sweep_kernel<ct, 1, ml>, nc_sweep_kernel<ct, 2, ml>, nc_sweep_kernel<ct, 3, ml>, nc_sweep_kernel<ct, 4, ml>, \
+                        nc_sweep_kernel<ct, 5, ml>, nc_sweep_kernel<ct, 6, ml>, nc_sweep_kernel<ct, 7, ml>, nc_sweep_kernel<ct, 8, ml>}
+// [0]: softmax against one class per row, [1]: per-class sigmoid against a multi-hot mask
+const SweepFn nc_sweeps[2][4][8] = {{NC_ROW(1, false), NC_ROW(2, false), NC_ROW(3, false), NC_ROW(4, false)},
+                                    {NC_ROW(1, true), NC_ROW(2, true), NC_ROW(3, true), NC_ROW(4, true)}};
 
 // The launch plan of a sweep: template instance, grid (a function of m alone), dynamic LDS and the W k-chunk.
 struct SweepPlan {
@@ -343,13 +434,13 @@ struct SweepPlan {
     size_t lds;
 };
 
-SweepPlan sweep_plan(int64_t m, int C, int ld) {
+SweepPlan sweep_plan(int64_t m, int C, int ld, bool ml) {
     const int CT = cdiv(C, 32), DT = cdiv(ld, 32);
     const size_t fixed = sizeof(float) * NC_RT * ((size_t)(32 * DT + 1) + (32 * CT + 1));
     int KW = (int)((NC_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;
     KW = KW >= ld ? ld : (KW / 4) * 4;
     SweepPlan p;
-    p.fn = nc_sweeps[CT - 1][DT - 1];
+    p.fn = nc_sweeps[ml ? 1 : 0][CT - 1][DT - 1];
     p.grid = (int)std::min<int64_t>(NC_MAX_GRID, (m + NC_RT - 1) / NC_RT);
     p.KW = KW;
     p.lds = fixed + sizeof(float) * 32 * CT * (size_t)(KW + 1);
@@ -380,17 +471,34 @@ int check_labels(gg_ctx *ctx, const char *fn, const int32_t *labels, int64_t m, 
     return GG_OK;
 }
 
-// nodes, labels, theta = (W, b) on the device; the stage and the gradient
-hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, const int32_t *nodes, const int32_t *labels, int64_t m, int C, const float *W, const float *b) {
+// multi-hot masks [m][CW]: no bit at a position >= n_class
+int check_label_bits(gg_ctx *ctx, const char *fn, const uint32_t *bits, int64_t m, int n_class) {
+    GG_CHECK(ctx, bits != nullptr, GG_EINVAL, "%s: label_bits is NULL", fn);
+    const int CW = cdiv(n_class, 32), tail = n_class & 31;
+    if (tail == 0) return GG_OK;
+    const uint32_t stray = ~0u << tail;
+    for (int64_t i = 0; i < m; ++i) {
+        const uint32_t w = bits[i * CW + CW - 1] & stray;
+        GG_CHECK(ctx, w == 0, GG_EINVAL, "%s: label_bits row %lld has bit %d set, outside [0, n_class = %d)", fn, (long long)i,
+                 32 * (CW - 1) + __builtin_ctz(w), n_class);
+    }
+    return GG_OK;
+}
+
+// nodes, labels (one int32 class per row, or with `ml` the mask words uint32 [m][ceil(C / 32)]), theta = (W, b) on the device;
+// the stage and the gradient
+hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, bool ml, const int32_t *nodes, const void *labels, int64_t m, int C, const float *W,
+                      const float *b) {
     const int d = ctx->n_emb;
     const size_t cd = (size_t)C * d, n_par = cd + C;
+    const size_t label_bytes = sizeof(int32_t) * (size_t)m * (ml ? cdiv(C, 32) : 1);
     hipError_t e = f.nodes.reserve(sizeof(int32_t) * m);
-    if (e == hipSuccess) e = f.labels.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = f.labels.reserve(label_bytes);
     if (e == hipSuccess) e = f.theta.reserve(sizeof(float) * n_par);
     if (e == hipSuccess) e = f.grad.reserve(sizeof(float) * (n_par + 1));
     if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (n_par + 1) * p.grid);
     if (e == hipSuccess) e = hipMemcpyAsync(f.nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(f.labels.p, labels, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.labels.p, labels, label_bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && p.lds > 48 * 1024) e = hipFuncSetAttribute((const void *)p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
@@ -401,32 +509,32 @@ hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, const int32_t *no
 void enqueue_lossgrad(gg_ctx *ctx, const Fit &f, const SweepPlan &p, int which, int64_t m, int C, float l2, float *loss_dev) {
     const int d = ctx->n_emb;
     const int64_t cd = (int64_t)C * d;
-    SweepArgs a{ctx->model[which].E, f.nodes.as<int32_t>(), f.labels.as<int32_t>(), m, ctx->ld, d, C, f.theta.as<float>(), f.theta.as<float>() + cd, p.KW, f.part.as<float>()};
+    SweepArgs a{ctx->model[which].E, f.nodes.as<int32_t>(), f.labels.as<int32_t>(), m, ctx->ld, d, C, f.theta.as<float>(), f.theta.as<float>() + cd, p.KW,
+                f.part.as<float>(), f.labels.as<uint32_t>()};
     hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(256), p.lds, ctx->stream, a);
     hipLaunchKernelGGL(nc_reduce_kernel, dim3(cdiv(cd + C, NC_RED_COLS) + 1), dim3(256), 0, ctx->stream, f.part.as<float>(), p.grid, C, d, m,
                        f.theta.as<float>(), l2, f.grad.as<float>(), loss_dev);
 }
 
-}  // namespace
+// the labels of either variant: `ml` false -- one class per row, true -- the mask words
+int check_any_labels(gg_ctx *ctx, const char *fn, bool ml, const void *labels, int64_t m, int n_class) {
+    return ml ? check_label_bits(ctx, fn, (const uint32_t *)labels, m, n_class) : check_labels(ctx, fn, (const int32_t *)labels, m, n_class);
+}
 
-}  // namespace gg
-
-using namespace gg;
-
-// gg_classifier_lossgrad: see include/graphgan_hip.h.
-extern "C" int gg_classifier_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, const float *W,
-                                      const float *b, float l2, float *loss_out, float *gW_out, float *gb_out) {
+// gg_classifier_lossgrad / gg_classifier_ml_lossgrad (fn names the entry point in the error texts)
+int lossgrad_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t *nodes, const void *labels, int64_t m, int n_class, const float *W,
+                  const float *b, float l2, float *loss_out, float *gW_out, float *gb_out) {
     if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    if (const int rc = check_common(ctx, "gg_classifier_lossgrad", which, nodes, m, n_class)) return rc;
-    if (const int rc = check_labels(ctx, "gg_classifier_lossgrad", labels, m, n_class)) return rc;
-    GG_CHECK(ctx, W && b && loss_out && gW_out && gb_out, GG_EINVAL, "gg_classifier_lossgrad: W, b, loss_out, gW_out, gb_out must not be NULL");
-    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "gg_classifier_lossgrad: l2 must be finite and >= 0");
+    if (const int rc = check_common(ctx, fn, which, nodes, m, n_class)) return rc;
+    if (const int rc = check_any_labels(ctx, fn, ml, labels, m, n_class)) return rc;
+    GG_CHECK(ctx, W && b && loss_out && gW_out && gb_out, GG_EINVAL, "%s: W, b, loss_out, gW_out, gb_out must not be NULL", fn);
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
     GG_HIP(ctx, hipSetDevice(ctx->device));
     const int C = n_class;
     const size_t cd = (size_t)C * ctx->n_emb;
-    const SweepPlan p = sweep_plan(m, C, ctx->ld);
+    const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    hipError_t e = fit_upload(ctx, f, p, nodes, labels, m, C, W, b);
+    hipError_t e = fit_upload(ctx, f, p, ml, nodes, labels, m, C, W, b);
     if (e == hipSuccess) {
         enqueue_lossgrad(ctx, f, p, which, m, C, l2, nullptr);
         e = hipGetLastError();
@@ -436,26 +544,26 @@ extern "C" int gg_classifier_lossgrad(gg_ctx *ctx, int which, const int32_t *nod
     if (e == hipSuccess) e = hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     f.release();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_lossgrad: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e));
     return GG_OK;
 }
 
-// gg_classifier_fit: see include/graphgan_hip.h.
-extern "C" int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, int iters, float lr,
-                                 float l2, float *W_inout, float *b_inout, float *loss_out, double *ms_out) {
+// gg_classifier_fit / gg_classifier_ml_fit
+int fit_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t *nodes, const void *labels, int64_t m, int n_class, int iters, float lr,
+             float l2, float *W_inout, float *b_inout, float *loss_out, double *ms_out) {
     if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    if (const int rc = check_common(ctx, "gg_classifier_fit", which, nodes, m, n_class)) return rc;
-    if (const int rc = check_labels(ctx, "gg_classifier_fit", labels, m, n_class)) return rc;
-    GG_CHECK(ctx, W_inout && b_inout, GG_EINVAL, "gg_classifier_fit: W_inout and b_inout must not be NULL");
-    GG_CHECK(ctx, iters >= 1 && iters <= 1000000, GG_EINVAL, "gg_classifier_fit: iters = %d outside [1, 1000000]", iters);
-    GG_CHECK(ctx, lr > 0.f && std::isfinite(lr), GG_EINVAL, "gg_classifier_fit: lr must be finite and > 0");
-    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "gg_classifier_fit: l2 must be finite and >= 0");
+    if (const int rc = check_common(ctx, fn, which, nodes, m, n_class)) return rc;
+    if (const int rc = check_any_labels(ctx, fn, ml, labels, m, n_class)) return rc;
+    GG_CHECK(ctx, W_inout && b_inout, GG_EINVAL, "%s: W_inout and b_inout must not be NULL", fn);
+    GG_CHECK(ctx, iters >= 1 && iters <= 1000000, GG_EINVAL, "%s: iters = %d outside [1, 1000000]", fn, iters);
+    GG_CHECK(ctx, lr > 0.f && std::isfinite(lr), GG_EINVAL, "%s: lr must be finite and > 0", fn);
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
     GG_HIP(ctx, hipSetDevice(ctx->device));
     const int C = n_class;
     const size_t cd = (size_t)C * ctx->n_emb, n_par = cd + C;
-    const SweepPlan p = sweep_plan(m, C, ctx->ld);
+    const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    hipError_t e = fit_upload(ctx, f, p, nodes, labels, m, C, W_inout, b_inout);
+    hipError_t e = fit_upload(ctx, f, p, ml, nodes, labels, m, C, W_inout, b_inout);
     if (e == hipSuccess) e = f.mom.reserve(sizeof(float) * n_par);
     if (e == hipSuccess) e = f.var.reserve(sizeof(float) * n_par);
     if (e == hipSuccess) e = f.loss.reserve(sizeof(float) * iters);
@@ -481,9 +589,36 @@ extern "C" int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, c
     float ms = 0.f;
     if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     f.release();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_fit: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e));
     if (ms_out) *ms_out = ms;
     return GG_OK;
+}
+
+}  // namespace
+
+}  // namespace gg
+
+using namespace gg;
+
+// gg_classifier_lossgrad, gg_classifier_fit and their multi-label forms: see include/graphgan_hip.h.
+extern "C" int gg_classifier_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, const float *W,
+                                      const float *b, float l2, float *loss_out, float *gW_out, float *gb_out) {
+    return lossgrad_call(ctx, "gg_classifier_lossgrad", false, which, nodes, labels, m, n_class, W, b, l2, loss_out, gW_out, gb_out);
+}
+
+extern "C" int gg_classifier_ml_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const uint32_t *label_bits, int64_t m, int n_class,
+                                         const float *W, const float *b, float l2, float *loss_out, float *gW_out, float *gb_out) {
+    return lossgrad_call(ctx, "gg_classifier_ml_lossgrad", true, which, nodes, label_bits, m, n_class, W, b, l2, loss_out, gW_out, gb_out);
+}
+
+extern "C" int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *labels, int64_t m, int n_class, int iters, float lr,
+                                 float l2, float *W_inout, float *b_inout, float *loss_out, double *ms_out) {
+    return fit_call(ctx, "gg_classifier_fit", false, which, nodes, labels, m, n_class, iters, lr, l2, W_inout, b_inout, loss_out, ms_out);
+}
+
+extern "C" int gg_classifier_ml_fit(gg_ctx *ctx, int which, const int32_t *nodes, const uint32_t *label_bits, int64_t m, int n_class, int iters,
+                                    float lr, float l2, float *W_inout, float *b_inout, float *loss_out, double *ms_out) {
+    return fit_call(ctx, "gg_classifier_ml_fit", true, which, nodes, label_bits, m, n_class, iters, lr, l2, W_inout, b_inout, loss_out, ms_out);
 }
 
 // gg_classifier_predict: see include/graphgan_hip.h.
@@ -517,5 +652,46 @@ extern "C" int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *node
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     rel();
     if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_predict: %s", hipGetErrorString(e));
+    return GG_OK;
+}
+
+// gg_classifier_ml_predict: see include/graphgan_hip.h.
+extern "C" int gg_classifier_ml_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
+                                        const int32_t *k, uint32_t *pred_bits, float *logits_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_common(ctx, "gg_classifier_ml_predict", which, nodes, m, n_class)) return rc;
+    GG_CHECK(ctx, W && b && pred_bits, GG_EINVAL, "gg_classifier_ml_predict: W, b and pred_bits must not be NULL");
+    if (k)
+        for (int64_t i = 0; i < m; ++i)
+            GG_CHECK(ctx, k[i] >= 0 && k[i] <= n_class, GG_EINVAL, "gg_classifier_ml_predict: k = %d (row %lld) outside [0, n_class = %d]", k[i],
+                     (long long)i, n_class);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int C = n_class, d = ctx->n_emb, ld = ctx->ld, CW = cdiv(C, 32);
+    const size_t cd = (size_t)C * d;
+    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld + 4 * (size_t)NC_MAX_C);
+    DevBuf d_nodes, d_theta, d_k, d_pred, d_logits;
+    auto rel = [&]() { d_nodes.release(); d_theta.release(); d_k.release(); d_pred.release(); d_logits.release(); };
+    hipError_t e = d_nodes.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = d_theta.reserve(sizeof(float) * (cd + C));
+    if (e == hipSuccess && k) e = d_k.reserve(sizeof(int32_t) * m);
+    if (e == hipSuccess) e = d_pred.reserve(sizeof(uint32_t) * (size_t)m * CW);
+    if (e == hipSuccess && logits_out) e = d_logits.reserve(sizeof(float) * (size_t)m * C);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && k) e = hipMemcpyAsync(d_k.p, k, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute((const void *)nc_ml_predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+        const int grid = (int)std::min<int64_t>(1024, (m + 3) / 4);
+        hipLaunchKernelGGL(nc_ml_predict_kernel, dim3(grid), dim3(256), lds, ctx->stream, ctx->model[which].E, ld, d, d_nodes.as<int32_t>(), m, C,
+                           d_theta.as<float>(), d_theta.as<float>() + cd, k ? d_k.as<int32_t>() : nullptr, d_pred.as<uint32_t>(),
+                           logits_out ? d_logits.as<float>() : nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(pred_bits, d_pred.p, sizeof(uint32_t) * (size_t)m * CW, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && logits_out) e = hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m * C, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    rel();
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_ml_predict: %s", hipGetErrorString(e));
     return GG_OK;
 }

@@ -23,6 +23,25 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def pack_label_bits(Y, n_class):
+    """bool / 0-1 matrix [m, C] -> the multi-hot mask of gg_classifier_ml_*: uint32 [m, ceil(C / 32)], bit c & 31 of word c >> 5
+    = Y[i, c]."""
+    Y = np.asarray(Y).astype(bool)
+    C, CW = int(n_class), (int(n_class) + 31) // 32
+    if Y.ndim != 2 or Y.shape[1] != C:
+        raise ValueError("pack_label_bits: expected a matrix [m, %d], got %r" % (C, Y.shape))
+    m = Y.shape[0]
+    padded = np.zeros((m, 32 * CW), dtype=bool)
+    padded[:, :C] = Y
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").astype(np.uint32, copy=False).reshape(m, CW)
+
+
+def unpack_label_bits(bits, n_class):
+    """the inverse of ``pack_label_bits``: uint32 [m, ceil(C / 32)] -> bool [m, C]"""
+    bits = np.ascontiguousarray(bits, dtype="<u4")
+    return np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")[:, :int(n_class)].astype(bool)
+
+
 def graph_to_csr(n_node, graph):
     """Adjacency dict of ``utils.read_edges`` -> (rowptr int64 [N+1], col int32), list order kept."""
     deg = np.fromiter((len(graph.get(v, ())) for v in range(n_node)), dtype=np.int64, count=n_node)
@@ -624,6 +643,85 @@ class Engine:
         pred = np.empty(len(nodes_a), dtype=np.int32)
         z = np.empty((len(nodes_a), C), dtype=np.float32) if logits else None
         self._ck(lib.gg_classifier_predict(self._ctx, which, _ptr(nodes_a), len(nodes_a), C, _ptr(W), _ptr(b), _ptr(pred), _ptr(z)))
+        return (pred, z) if logits else pred
+
+    # ------------------------------------------------------------------ multi-label node classification (gg_classifier_ml_*)
+    def _nc_label_bits(self, fn, labels, m, n_class):
+        """labels as a bool / 0-1 matrix [m, C] or as packed uint32 [m, CW] -> packed uint32 [m, CW], no bit at a position >= C"""
+        C, CW = int(n_class), (int(n_class) + 31) // 32
+        a = np.asarray(labels)
+        if a.ndim == 2 and a.shape == (m, CW) and a.dtype == np.uint32:
+            if C % 32 and np.any(a[:, -1] >> np.uint32(C % 32)):
+                row = int(np.flatnonzero(a[:, -1] >> np.uint32(C % 32))[0])
+                raise ValueError("%s: label_bits row %d has a bit set at a position >= n_class = %d" % (fn, row, C))
+            return np.ascontiguousarray(a)
+        if a.ndim != 2 or a.shape != (m, C) or not (a.dtype == np.bool_ or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("%s: labels must be a bool / 0-1 matrix [%d, %d] or packed uint32 [%d, %d], got %s %r"
+                             % (fn, m, C, m, CW, a.dtype, a.shape))
+        if a.dtype != np.bool_ and a.size and (int(a.min()) < 0 or int(a.max()) > 1):
+            raise ValueError("%s: the label matrix must hold 0 and 1 only" % fn)
+        return pack_label_bits(a, C)
+
+    def classifier_ml_lossgrad(self, nodes, labels, W, b, which=0, l2=0.0):
+        """Loss and gradients of one-vs-rest logistic regression (per-class sigmoid cross-entropy, every class normalised by the
+        row count) on the rows ``nodes`` of table ``which`` at (W [C, n_emb], b [C]); ``labels`` is a bool / 0-1 matrix [m, C] or
+        packed uint32 [m, ceil(C / 32)] (gg_classifier_ml_lossgrad: the fused sweep on the device).  Returns dict(loss, gW, gb)."""
+        W, b = self._nc_params("classifier_ml_lossgrad", W, b)
+        C = int(W.shape[0])
+        nodes_a, _ = self._nc_args("classifier_ml_lossgrad", nodes, which, C)
+        bits = self._nc_label_bits("classifier_ml_lossgrad", labels, len(nodes_a), C)
+        loss = np.zeros(1, dtype=np.float32)
+        gW = np.empty_like(W)
+        gb = np.empty_like(b)
+        self._ck(lib.gg_classifier_ml_lossgrad(self._ctx, which, _ptr(nodes_a), _ptr(bits), len(nodes_a), C, _ptr(W), _ptr(b), float(l2),
+                                               _ptr(loss), _ptr(gW), _ptr(gb)))
+        return dict(loss=float(loss[0]), gW=gW, gb=gb)
+
+    def classifier_ml_fit(self, nodes, labels, n_class, which=0, iters=200, lr=0.05, l2=1e-4, W=None, b=None):
+        """``iters`` steps of full-batch Adam on the one-vs-rest loss of the rows ``nodes`` of table ``which``
+        (gg_classifier_ml_fit), from zeros unless (W, b) are given; labels as in ``classifier_ml_lossgrad``.  Returns
+        dict(W fp32 [n_class, n_emb], b fp32 [n_class], loss fp32 [iters] -- the loss before each update --, ms)."""
+        nodes_a, _ = self._nc_args("classifier_ml_fit", nodes, which, n_class)
+        C = int(n_class)
+        bits = self._nc_label_bits("classifier_ml_fit", labels, len(nodes_a), C)
+        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
+            raise ValueError("classifier_ml_fit: iters must be an integer >= 1, got %r" % (iters,))
+        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
+            raise ValueError("classifier_ml_fit: lr must be > 0 and l2 >= 0, got %r and %r" % (lr, l2))
+        if (W is None) != (b is None):
+            raise ValueError("classifier_ml_fit: give both W and b, or neither")
+        if W is None:
+            W, b = np.zeros((C, self.n_emb), dtype=np.float32), np.zeros(C, dtype=np.float32)
+        else:
+            W, b = self._nc_params("classifier_ml_fit", W, b)
+            if W.shape[0] != C:
+                raise ValueError("classifier_ml_fit: W has %d rows, n_class is %d" % (W.shape[0], C))
+            W, b = W.copy(), b.copy()
+        loss = np.empty(int(iters), dtype=np.float32)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_classifier_ml_fit(self._ctx, which, _ptr(nodes_a), _ptr(bits), len(nodes_a), C, int(iters), float(lr), float(l2),
+                                          _ptr(W), _ptr(b), _ptr(loss), ctypes.byref(ms)))
+        return dict(W=W, b=b, loss=loss, ms=ms.value)
+
+    def classifier_ml_predict(self, nodes, W, b, which=0, k=None, logits=False):
+        """The label sets of the rows ``nodes`` of table ``which`` under (W, b) (gg_classifier_ml_predict).  With ``k`` (one
+        integer in [0, C] per row): the first k[i] classes of row i in the order (logit descending, class ascending); without:
+        the classes whose logit is > 0.  Returns pred bool [len(nodes), C], or (pred, logits fp32 [len(nodes), C])."""
+        W, b = self._nc_params("classifier_ml_predict", W, b)
+        C = int(W.shape[0])
+        nodes_a, _ = self._nc_args("classifier_ml_predict", nodes, which, C)
+        k_a = None
+        if k is not None:
+            k_a = np.asarray(k)
+            if k_a.shape != nodes_a.shape or not np.issubdtype(k_a.dtype, np.integer):
+                raise ValueError("classifier_ml_predict: k must be integers, one per node")
+            if int(k_a.min()) < 0 or int(k_a.max()) > C:
+                raise ValueError("classifier_ml_predict: k outside [0, n_class = %d]" % C)
+            k_a = _i32(k_a)
+        bits = np.empty((len(nodes_a), (C + 31) // 32), dtype=np.uint32)
+        z = np.empty((len(nodes_a), C), dtype=np.float32) if logits else None
+        self._ck(lib.gg_classifier_ml_predict(self._ctx, which, _ptr(nodes_a), len(nodes_a), C, _ptr(W), _ptr(b), _ptr(k_a), _ptr(bits), _ptr(z)))
+        pred = unpack_label_bits(bits, C)
         return (pred, z) if logits else pred
 
     def get_embeddings(self, which):

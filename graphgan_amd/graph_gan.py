@@ -460,15 +460,18 @@ class GraphGAN(object):
                 results.append(rec.format_results(cfg.modes[i], re_.eval_recommendation(), ks))
         elif cfg.app == "node_classification":
             # accuracy / Macro-F1 of softmax regression on the frozen rows, fitted and applied on the device (gg_classifier_*); one
-            # line per mode: "gen:acc=<a> macro_f1=<f> n_train=<n> n_test=<n>"
+            # line per mode: "gen:acc=<a> macro_f1=<f> n_train=<n> n_test=<n>".  With engine_nc_multilabel: one-vs-rest logistic
+            # regression on "node label [label ...]" files (gg_classifier_ml_*), "gen:acc=<a> micro_f1=<f> macro_f1=<f> n_train= n_test="
             if not hasattr(cfg, "labels_filename"):
                 raise ValueError("app = 'node_classification' needs config.labels_filename (lines of 'node label')")
+            multilabel = bool(_cfg(cfg, "engine_nc_multilabel", False))
             for i in range(2):
                 nce = nc.NodeClassifyEval(cfg.emb_filenames[i], cfg.labels_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i,
                                           train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed,
                                           iters=int(_cfg(cfg, "engine_nc_iters", 200)), lr=float(_cfg(cfg, "engine_nc_lr", 0.05)),
-                                          l2=float(_cfg(cfg, "engine_nc_l2", 1e-4)))
-                results.append(nc.format_results(cfg.modes[i], nce.eval_node_classification()))
+                                          l2=float(_cfg(cfg, "engine_nc_l2", 1e-4)), multilabel=multilabel,
+                                          ml_protocol=_cfg(cfg, "engine_nc_ml_protocol", "topk"))
+                results.append((nc.format_ml_results if multilabel else nc.format_results)(cfg.modes[i], nce.eval_node_classification()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -55,6 +55,38 @@ def read_labels(filename, n_node):
     return nodes, classes.astype(np.int64).reshape(-1), values.astype(np.int64)
 
 
+MAX_LABELS = 128  # the classifier's class limit (include/graphgan_hip.h, gg_classifier_*)
+
+
+def read_multilabels(filename, n_node):
+    """Lines of ``node label [label ...]`` (any whitespace, integer labels of any value; blank lines are skipped).  A node may
+    appear on several lines: its labels are the union, a repeated (node, label) is harmless.
+    -> (nodes int64 sorted, Y bool [L, C], label_values int64 [C] sorted): ``Y[i, c]`` says that ``nodes[i]`` has the label
+    whose rank among the distinct label values is c.  An id outside [0, n_node), a line with fewer than two tokens or more than
+    128 distinct labels raises ValueError."""
+    seen = {}
+    with open(filename, "r") as f:
+        for no, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) < 2:
+                raise ValueError("%s:%d: expected 'node label [label ...]', got %r" % (filename, no, line.strip()))
+            node = int(tok[0])
+            if not 0 <= node < n_node:
+                raise ValueError("%s:%d: node id %d outside [0, %d)" % (filename, no, node, n_node))
+            seen.setdefault(node, set()).update(int(t) for t in tok[1:])
+    nodes = np.array(sorted(seen), dtype=np.int64)
+    values = np.array(sorted(set().union(*seen.values())) if seen else [], dtype=np.int64)
+    if len(values) > MAX_LABELS:
+        raise ValueError("%s: %d distinct labels, the classifier takes at most %d" % (filename, len(values), MAX_LABELS))
+    rank = {int(v): c for c, v in enumerate(values.tolist())}
+    Y = np.zeros((len(nodes), len(values)), dtype=bool)
+    for i, v in enumerate(nodes.tolist()):
+        Y[i, [rank[x] for x in seen[v]]] = True
+    return nodes, Y, values
+
+
 def read_embeddings(filename, n_node, n_embed):
     """``.emb`` text -> float64 [n_node, n_embed]; the first line is a header; rows whose id is
     absent keep uniform [0, 1) draws from the global numpy RNG (utils.py:57-67)."""

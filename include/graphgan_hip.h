@@ -425,6 +425,32 @@ int gg_classifier_fit(gg_ctx *ctx, int which, const int32_t *nodes, const int32_
 int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
                           int32_t *pred_out, float *logits_out /* NULL or [m, n_class] */);
 
+/* ---- multi-label node classification (additive entry points; GG_ABI_VERSION stays 9).  The paper's labelled datasets
+ * (BlogCatalog, Wikipedia) give a node several labels: one-vs-rest logistic regression, one binary problem per class, on the
+ * same frozen rows, under the limits of gg_classifier_* above.  Labels are a multi-hot mask label_bits uint32 [m][CW],
+ * CW = ceil(n_class / 32): bit c & 31 of word c >> 5 is set when row i has class c.  A row with no label, or with every label,
+ * is legal; a bit at a position >= n_class is GG_EINVAL (the text names the row and the bit).
+ *   z_i  = W . E[nodes[i]] + b,   y_ic = bit c of row i
+ *   loss = (1/m) sum_i sum_c [softplus(z_ic) - y_ic z_ic] + (l2 / 2) |W|^2    (every class normalised by m; the bias is not regularised)
+ *   gW   = (1/m) sum_i (sigmoid(z_i) - y_i) E[nodes[i]]^T + l2 W,   gb = (1/m) sum_i (sigmoid(z_i) - y_i)
+ * in the stable forms, with e = exp(-|z|): softplus(z) = max(z, 0) + log1p(e), sigmoid(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e).
+ * A logit of +-200 gives a finite loss and a gradient entry of exactly 0 - y or 1 - y; the loss at zero parameters is
+ * n_class log 2.
+ * gg_classifier_ml_lossgrad / gg_classifier_ml_fit: as gg_classifier_lossgrad / gg_classifier_fit -- the same fused sweep (its
+ *   per-row loss stage is the only difference), the same stage and reduction, the same Adam (constants, bias correction, step
+ *   count; loss_out[t] = the loss BEFORE update t) and the same determinism: a grid that depends on m alone, partials added in a
+ *   fixed order, no floating-point atomics, the same inputs give the same bits.
+ * gg_classifier_ml_predict: pred_bits [m][CW] in the layout of label_bits; logits_out (may be NULL) [m, n_class].  The classes
+ *   of a row are totally ordered by logit descending, then class ascending.  With k [m]: row i gets the first k[i] classes of
+ *   that order (the customary protocol passes the row's true label count); 0 <= k[i] <= n_class, otherwise GG_EINVAL naming the
+ *   row.  With k == NULL: the classes with z > 0, strictly (an exact 0 is not predicted).  Unspecified on non-finite logits. */
+int gg_classifier_ml_lossgrad(gg_ctx *ctx, int which, const int32_t *nodes, const uint32_t *label_bits, int64_t m, int n_class,
+                              const float *W, const float *b, float l2, float *loss_out, float *gW_out, float *gb_out);
+int gg_classifier_ml_fit(gg_ctx *ctx, int which, const int32_t *nodes, const uint32_t *label_bits, int64_t m, int n_class,
+                         int iters, float lr, float l2, float *W_inout, float *b_inout, float *loss_out /* [iters] or NULL */, double *ms_out);
+int gg_classifier_ml_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
+                             const int32_t *k /* [m] or NULL */, uint32_t *pred_bits /* [m][CW] */, float *logits_out /* NULL or [m, n_class] */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);

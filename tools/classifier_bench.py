@@ -5,11 +5,14 @@ itself once more with --torch-leg (a fresh child process: torch ships a HIP runt
 one process) and reads the child's time.  A baseline that cannot run fails the tool: there is no result without it.
     python tools/classifier_bench.py [n_node] [n_emb] [n_class] [m]        (default 10^6 128 40 900000)
     python tools/classifier_bench.py --engine-only ...                     (the engine's legs alone, for a profiler)
+    python tools/classifier_bench.py --multilabel ...                      (also the one-vs-rest fit, gg_classifier_ml_fit, in the same run)
 One JSON line: ms per iteration of a fit (sweep + stage reduction + Adam: HIP events around the enqueued iterations, divided by
 their number -- an upper bound of the sweep alone), ms per fit of the default 200 iterations, the fractions of the HBM model
 (m d 4 B per sweep at 8 TB/s) and of the flop model (4 m d C per sweep at the 155 TFLOP/s that v_mfma_f32_32x32x2_f32 sustains on
 the MI355X: 157.3 TFLOP/s by specification, 64 cycles per SIMD and instruction), the torch baseline (index_select, two matmuls, one
-softmax; best of 5, torch.cuda events) and the ratio to it, and a parity leg against float64 numpy on 4 096 of the rows."""
+softmax; best of 5, torch.cuda events) and the ratio to it, and a parity leg against float64 numpy on 4 096 of the rows.
+With --multilabel the same rows get 1-3 labels each and the sigmoid variant of the sweep is timed the same way (3 warm-up
+iterations, best of 3 x 20) beside the softmax variant: ml_ms_per_iteration, the ratio of the two, and its own parity leg."""
 import json
 import os
 import subprocess
@@ -99,6 +102,27 @@ p = np.exp(z) / np.exp(z).sum(axis=1, keepdims=True)
 p[np.arange(4096), labels[sub]] -= 1.0
 out["parity_gW_max_abs_diff"] = float(np.max(np.abs(got["gW"] - (p.T @ X / 4096 + 1e-4 * W))))
 out["loss_at_parity_params"] = float(eng.classifier_lossgrad(nodes, labels, W, b)["loss"])
+if "--multilabel" in flags:
+    Y = np.zeros((m, C), dtype=bool)
+    Y[np.arange(m), labels] = True
+    for extra in range(2):  # a second and a third label on a third of the rows each (a draw that repeats a label adds none)
+        pick = rs.random(m) < 1.0 / 3.0
+        Y[np.flatnonzero(pick), rs.integers(0, C, int(pick.sum()))] = True
+    from graphgan_amd.engine import pack_label_bits
+    bits = pack_label_bits(Y, C)
+    eng.classifier_ml_fit(nodes, bits, C, iters=3)  # warm-up
+    ml_ms = min(eng.classifier_ml_fit(nodes, bits, C, iters=20)["ms"] / 20 for _ in range(3))
+    ml_fit = eng.classifier_ml_fit(nodes, bits, C, iters=200)
+    got = eng.classifier_ml_lossgrad(nodes[sub], bits[sub], W, b, l2=1e-4)
+    z = X @ W.astype(np.float64).T + b
+    e = np.exp(-np.abs(z))
+    p = np.where(z >= 0, 1.0, e) / (1.0 + e) - Y[sub]
+    out.update({"ml_workload": "one-vs-rest logistic regression on the same rows, %.2f labels per row" % Y.sum(axis=1).mean(),
+                "ml_ms_per_iteration": ml_ms, "ml_ms_per_fit_200": ml_fit["ms"], "ml_loss_first": float(ml_fit["loss"][0]),
+                "ml_loss_last": float(ml_fit["loss"][-1]), "ratio_ml_to_softmax_iteration": ml_ms / it_ms,
+                "ml_parity_gW_max_abs_diff": float(np.max(np.abs(got["gW"] - (p.T @ X / 4096 + 1e-4 * W)))),
+                "ml_parity_loss_abs_diff": abs(got["loss"] - float((np.maximum(z, 0) + np.log1p(e) - Y[sub] * z).sum() / 4096
+                                                                   + 0.5e-4 * (W.astype(np.float64) ** 2).sum()))})
 eng.close()
 if "--engine-only" not in flags:
     child = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-leg"] + args, capture_output=True, text=True)
