@@ -6,15 +6,18 @@
 // threads, 4 wavefronts) walks 64-row tiles; per tile
 //   1. the rows are gathered into LDS (Xs; the next tile's rows are already in flight to registers while this one computes),
 //   2. logits  Z[64, C] = Xs . W^T on v_mfma_f32_32x32x2_f32, W staged in LDS (Ws) once per workgroup -- in k-chunks per tile
-//      only where C x d does not fit beside the tile (C = 128 at d = 256),
+//      only where C x d does not fit beside the tile: C > 96 at ld > 152 and C > 64 at ld > 192 (sweep_plan; six of the
+//      32 (CT, DT) instances at full tiles: (4, 5 .. 8), (3, 7), (3, 8)),
 //   3. a max-subtracted softmax per row in LDS (4 threads per row), the row's loss term, P = p - onehot left in LDS (Ps),
 //   4. gradient  G[C, d] += P^T . Xs on the same matrix instruction, the accumulators in registers across all tiles of the
 //      workgroup; gb += column sums of Ps.
 // CT = ceil(C / 32) class tiles and DT = ceil(ld / 32) column tiles are template parameters: the accumulators are register
 // arrays with compile-time indices (an instantiation that spills fails the build, check_no_scratch.sh).
 // Determinism: the grid is min(NC_MAX_GRID, ceil(M / 64)) -- a function of M alone --, tiles go to workgroups round robin,
-// every workgroup writes its partial [C d + C + 1] to a stage and nc_reduce_kernel sums the stage in a fixed order.  No
-// floating-point atomics anywhere: two calls with the same inputs give the same bits.
+// every workgroup writes its partial [C d + C + 2] to a stage and nc_reduce_kernel sums the stage in a fixed order.  No
+// floating-point atomics anywhere: two calls with the same inputs give the same bits.  The loss partial is a float64 sum kept
+// as two floats (high part, remainder): one float would round a sum of 64 C-term rows at 2^-24 of ITS size, more than half a
+// float32 spacing of the mean loss at small M.
 // nc_adam_kernel: full-batch Adam on (W, b); nc_predict_kernel: logits + argmax (ties to the lowest class).
 //
 // Multi-label (gg_classifier_ml_*): one-vs-rest logistic regression against a multi-hot mask uint32 [M][CT] (bit c & 31 of word
@@ -54,7 +57,7 @@ struct SweepArgs {
     int ld, d, C;
     const float *W, *b;      // [C, d], [C]
     int KW;                  // k-chunk of the W staging (>= ld: W is staged once)
-    float *part;             // [grid][C d + C + 1]
+    float *part;             // [grid][C d + C + 2]: gW, gb, the loss as (high, remainder)
     const uint32_t *bits;    // [m][CT] multi-hot label mask (sigmoid variant)
 };
 
@@ -229,8 +232,8 @@ __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
         }
     }
 
-    // the workgroup's partial: gW [C, d], gb [C], loss
-    float *part = a.part + (int64_t)blockIdx.x * ((int64_t)C * d + C + 1);
+    // the workgroup's partial: gW [C, d], gb [C], loss (two floats)
+    float *part = a.part + (int64_t)blockIdx.x * ((int64_t)C * d + C + 2);
 #pragma unroll
     for (int i = 0; i < N2; ++i) {
         const int t = wv + 4 * i;
@@ -250,23 +253,28 @@ __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
         if (tid < w) red[tid] += red[tid + w];
         __syncthreads();
     }
-    if (tid == 0) part[(int64_t)C * d + C] = (float)red[0];
+    if (tid == 0) {
+        const float hi = (float)red[0];
+        part[(int64_t)C * d + C] = hi;
+        part[(int64_t)C * d + C + 1] = (float)(red[0] - (double)hi);
+    }
 }
 
 // grad[j] = (1/M) sum_g part[g][j] (+ l2 W[j] for j < C d) for the C d + C gradient entries: a workgroup takes NC_RED_COLS
 // entries, NC_RED_SLICES threads per entry sum contiguous slices of the stage, thread 0 of the entry adds the slices in order.
-// The LAST workgroup gives the loss: (1/M) sum_g part[g][C d + C] + (l2 / 2) |W|^2, both by strided sums and a fixed tree.
+// The LAST workgroup gives the loss: (1/M) sum_g (part[g][C d + C] + part[g][C d + C + 1]) + (l2 / 2) |W|^2, both by strided
+// sums and a fixed tree.
 __global__ __launch_bounds__(256) void nc_reduce_kernel(const float *part, int n_part, int C, int d, int64_t m, const float *W, float l2,
                                                        float *grad, float *loss_out) {
     __shared__ float sh[256];
     __shared__ double shd[256];
     const int tid = threadIdx.x;
-    const int64_t cd = (int64_t)C * d, n_out = cd + C, stride = n_out + 1;
+    const int64_t cd = (int64_t)C * d, n_out = cd + C, stride = n_out + 2;
     const float fm = (float)m;
     if (blockIdx.x == gridDim.x - 1) {
         double sl = 0.0;  // (the loss terms in float64, as in the sweep)
         float sw = 0.f;
-        for (int g = tid; g < n_part; g += 256) sl += (double)part[(int64_t)g * stride + n_out];
+        for (int g = tid; g < n_part; g += 256) sl += (double)part[(int64_t)g * stride + n_out] + (double)part[(int64_t)g * stride + n_out + 1];
         for (int64_t j = tid; j < cd; j += 256) sw += W[j] * W[j];
         shd[tid] = sl;
         __syncthreads();
@@ -496,7 +504,7 @@ hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, bool ml, const in
     if (e == hipSuccess) e = f.labels.reserve(label_bytes);
     if (e == hipSuccess) e = f.theta.reserve(sizeof(float) * n_par);
     if (e == hipSuccess) e = f.grad.reserve(sizeof(float) * (n_par + 1));
-    if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (n_par + 1) * p.grid);
+    if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (n_par + 2) * p.grid);
     if (e == hipSuccess) e = hipMemcpyAsync(f.nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.labels.p, labels, label_bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(f.theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 N_TABLE = 5000
 # (M, d, C): row counts around the 64-row tile, d around the 32-column tiles (8 -> 1, 50 -> 2, 128 -> 4, 256 -> 8), C around the
-# 32-class tiles; (997, 256, 128) is the shape whose W is staged in k-chunks
+# 32-class tiles; (997, 256, 128) is the one shape HERE whose W is staged in k-chunks (the other chunked instances, C > 64 at
+# d > 192 and C > 96 at d > 152, are in test_gpu_classifier_shapes.py)
 LOSSGRAD_CASES = [(1, 8, 2), (63, 8, 5), (64, 8, 40), (65, 8, 128), (997, 8, 2),
                   (1, 50, 40), (63, 50, 128), (64, 50, 2), (65, 50, 5), (997, 50, 40),
                   (1, 128, 128), (63, 128, 2), (64, 128, 5), (65, 128, 40), (997, 128, 40), (997, 128, 128),

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 N_TABLE = 5000
 # (M, d, C): the 64-row tile edge (63, 64, 65), the 32-column tiles (d = 8 -> 1, 50 -> 2, 128 -> 4, 256 -> 8), the mask-word
-# edges (C = 31, 32, 33, 64, 65, 128); (997, 256, 128) is the shape whose W is staged in k-chunks
+# edges (C = 31, 32, 33, 64, 65, 128); (997, 256, 128) is the one shape HERE whose W is staged in k-chunks (the other chunked
+# instances, C > 64 at d > 192 and C > 96 at d > 152, are in test_gpu_classifier_shapes.py)
 LOSSGRAD_CASES = [(1, 8, 2), (63, 8, 31), (64, 8, 32), (65, 8, 33), (997, 50, 64), (65, 50, 65), (63, 128, 40), (997, 128, 128),
                   (64, 256, 5), (997, 256, 128)]
 
