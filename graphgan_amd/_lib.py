@@ -116,6 +116,7 @@ SIGNATURES = {
     "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
+    "gg_pretrain_set_walk_bias": (ctypes.c_int, [_P, _u32, _u32, _u32]),
     "gg_prepare_pretrain": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _i32, _i32, _u64, _u32, _P, _P, _P]),
     "gg_classifier_lossgrad": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _i64, ctypes.c_int, _P, _P, ctypes.c_float, _P, _P, _P]),
     "gg_classifier_fit": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),

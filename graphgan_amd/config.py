@@ -75,7 +75,7 @@ engine_nc_l2 = 1e-4
 # "threshold" the classes with a positive logit.
 engine_nc_multilabel = False
 engine_nc_ml_protocol = "topk"
-# skip-gram pre-training from uniform random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
+# skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False
 engine_pretrain_walks = 10    # walks per start node and epoch
@@ -85,4 +85,6 @@ engine_pretrain_neg = 5       # negatives per pair, drawn in proportion to round
 engine_pretrain_epochs = 1
 engine_pretrain_batch = 4096  # rows per optimizer step
 engine_pretrain_lr = 5e-3
+engine_pretrain_p = 1.0       # node2vec return parameter p and in-out parameter q, each in [1/16, 16] (pretrain.walk_bias);
+engine_pretrain_q = 1.0       # p = q = 1 is the uniform (DeepWalk) walk
 engine_pretrain_rows_per_call = 1 << 26  # rows one gg_prepare_pretrain call may produce (12 B each, device resident)

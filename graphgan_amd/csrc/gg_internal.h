@@ -290,7 +290,8 @@ struct gg_ctx {
     int64_t owner_min_bound = 4096;   // GG_COMM_OWNER_MIN: steps of fewer pairs never try it (its two host round trips outweigh a minibatch)
     int64_t comm_steps_owner = 0;     // optimizer steps that took it (gg_comm_stats counts them with the sparse steps)
 
-    // gg_topk_scores with exclude = 1 (topk_score.hip): the resident adjacency with every list sorted; dropped by gg_set_graph_csr
+    // gg_topk_scores with exclude = 1 (topk_score.hip) and the biased pre-training walks (pretrain.hip): the resident adjacency
+    // with every list sorted, built by ensure_sorted_adjacency on first use; dropped by gg_set_graph_csr
     gg::DevBuf topk_adj;
     bool topk_adj_valid = false;
 
@@ -307,6 +308,7 @@ struct gg_ctx {
     bool pt_noise_set = false;
     uint64_t pt_noise_total = 0;
     int32_t pt_sample_n = 0, pt_sample_stride = 1;
+    uint32_t pt_bias[3] = {1, 1, 1};   // (w_ret, w_com, w_out) of gg_pretrain_set_walk_bias; kept across gg_set_graph_csr
     hipEvent_t pt_ev[4] = {};          // HIP events around pt_walk_kernel / pt_fill_kernel (profiling cadence 1)
     bool ep_d_open = false;            // between gg_epoch_begin(reset_d) / a gg_epoch_add with do_d and gg_epoch_commit(1)
 
@@ -334,6 +336,7 @@ int fail(gg_ctx *ctx, int code, const char *fmt, ...);
 
 // exclusive scan of n int32 counts into n+1 int64 offsets (prepare.hip)
 int device_exclusive_scan(gg_ctx *ctx, const int32_t *cnt, int64_t *ptr, int64_t n);
+int ensure_sorted_adjacency(gg_ctx *ctx);  // topk_score.hip: ctx->topk_adj (every node's list sorted), built on first use
 int ensure_g_pairs(gg_ctx *ctx);  // prepare.hip: (node_1, node_2) of the resident G walks, written on first use
 int device_compact_flags(gg_ctx *ctx, const int32_t *flag, int64_t n, int32_t *list, int64_t *total_out);  // prepare.hip
 int device_segment_rows(gg_ctx *ctx, const int32_t *cnt, int64_t n, int T, int32_t *off, int4 *list, int64_t *totals, hipStream_t stream = nullptr,

@@ -1,11 +1,14 @@
 // pretrain.hip -- skip-gram pre-training rows on the device (gg_pretrain_set_noise / gg_prepare_pretrain):
-//   uniform random walks over the resident CSR -> window pairs -> negative samples -> (center, neighbor, label) rows
+//   uniform or node2vec-biased random walks over the resident CSR -> window pairs -> negative samples -> (center, neighbor, label) rows
 // in the buffers gg_d_pass trains the discriminator's table on (one-table skip-gram with negative sampling).  The reference
 // has no counterpart: its pre_train/*.emb files come from an external DeepWalk / node2vec run (src/GraphGAN/config.py:33-34).
-// The sampling contract P1-P5 (include/graphgan_hip.h) is exact integer arithmetic on the Philox uniforms of gg_arith.h, so
+// The sampling contract P1-P5 with the biased walk P2b (include/graphgan_hip.h) is exact integer arithmetic on the Philox uniforms of gg_arith.h, so
 // the rows do not depend on how the walks are spread over threads, waves or calls.  Nothing of size rows x 12 B crosses PCIe.
 //
 //   pt_walk_kernel    a thread per walk: walk_len dependent rowptr / col gathers (latency bound; parallel over the walks)
+//   pt_walk_bias_kernel  the node2vec walk of P2b (gg_pretrain_set_walk_bias with unequal weights): a thread per walk, up to 32
+//                     rejection trials per hop (a col gather and a binary search in the sorted list of the previous node each);
+//                     the hops whose trials all fail are drawn exactly by the whole wavefront, one such lane after the other
 //   pt_count_kernel   rows of each walk from its length -> device_exclusive_scan -> row offsets
 //   pt_fill_kernel    a wavefront per walk: path and per-centre pair offsets in LDS, lanes over the walk's rows, one Philox draw
 //                     and one search in the uint64 prefix sums per negative row, coalesced 4-byte stores
@@ -58,6 +61,128 @@ __global__ __launch_bounds__(256) void pt_walk_kernel(const int64_t *__restrict_
     }
     for (int h = len; h < walk_len; ++h) p[h] = -1;
     path_len[g] = len;
+}
+
+// P2b: the class weight of candidate x at a hop whose previous node is prev; sadj + [pe0, pe0 + pk) = the sorted list of prev.
+struct PtBias {
+    uint32_t w_ret, w_com, w_out, w_max;
+};
+
+__device__ __forceinline__ uint32_t pt_class_of(int32_t x, int32_t prev, const int32_t *__restrict__ sadj, int64_t pe0, int32_t pk,
+                                                const PtBias &b) {
+    if (x == prev) return b.w_ret;
+    int32_t lo = 0, hi = pk;  // the first entry >= x
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (sadj[pe0 + mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < pk && sadj[pe0 + lo] == x ? b.w_com : b.w_out;
+}
+
+constexpr int PT_TRIALS = 32;  // R of P2b
+
+// P1 + P2b.  A lane per walk like pt_walk_kernel, but every lane of a wavefront stays in the hop loop until the last walk of
+// the wavefront has ended (alive = 0 for the others): the exact draw behind PT_TRIALS rejections is made by all 64 lanes
+// together -- __ballot names the lanes that need one, __shfl hands their state round -- so no thread ever scans a hub's list alone.
+// The launch has whole wavefronts (256 threads a workgroup); lanes behind n_walks run along with valid = 0.
+__global__ __launch_bounds__(256) void pt_walk_bias_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                           const int32_t *__restrict__ sadj, const int32_t *__restrict__ starts,
+                                                           int64_t n_walks, int wps, int walk_len, uint64_t seed, uint32_t stream,
+                                                           PtBias bias, int32_t *__restrict__ paths, int32_t *__restrict__ path_len) {
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = g < n_walks;
+    const int64_t si = valid ? g / wps : 0;
+    const uint32_t w = valid ? (uint32_t)(g - si * wps) : 0u;
+    const int32_t s = valid ? starts[si] : 0;
+    int32_t *p = paths + (valid ? g : 0) * walk_len;
+    if (valid) p[0] = s;
+    int32_t cur = s, prev = -1, pk = 0;
+    int64_t pe0 = 0;  // the list of prev: the registers of the hop before
+    int len = 1;
+    bool alive = valid;
+    for (int h = 1; h < walk_len; ++h) {
+        if (__ballot(alive) == 0ull) break;  // (the same in every lane)
+        int64_t e0 = 0;
+        int32_t k = 0, nxt = -1;
+        bool exhausted = false;
+        if (alive) {
+            e0 = rowptr[cur];
+            k = (int32_t)(rowptr[cur + 1] - e0);
+            if (k == 0) {
+                alive = false;
+            } else if (h == 1 || k == 1) {  // P2 (k == 1: t(1) = 0 whatever the draw)
+                nxt = col[e0 + (k == 1 ? 0 : (int64_t)threshold(uniform53(seed, stream, (uint32_t)s, w, (uint32_t)h), (uint64_t)k))];
+            } else {
+                exhausted = true;
+                for (int r = 0; r < PT_TRIALS; ++r) {
+                    const uint32_t hop_c = r == 0 ? (uint32_t)h : 0x80000000u + 256u * (uint32_t)r + (uint32_t)h;
+                    const int32_t x = col[e0 + (int64_t)threshold(uniform53(seed, stream, (uint32_t)s, w, hop_c), (uint64_t)k)];
+                    const uint32_t c = pt_class_of(x, prev, sadj, pe0, pk, bias);
+                    bool take = c == bias.w_max;
+                    if (!take) {
+                        const uint32_t hop_a = 0x40000000u + 256u * (uint32_t)r + (uint32_t)h;
+                        take = threshold(uniform53(seed, stream, (uint32_t)s, w, hop_a), (uint64_t)bias.w_max) < (uint64_t)c;
+                    }
+                    if (take) {
+                        nxt = x;
+                        exhausted = false;
+                        break;
+                    }
+                }
+            }
+        }
+        // the exact draw, wave-cooperative: W = the class weights of the whole list of cur, t = t(W), the first entry whose
+        // inclusive prefix sum exceeds t
+        for (uint64_t todo = __ballot(exhausted); todo != 0ull; todo &= todo - 1) {
+            const int src = __ffsll((unsigned long long)todo) - 1;
+            const int64_t b_e0 = __shfl(e0, src, 64), b_pe0 = __shfl(pe0, src, 64);
+            const int32_t b_k = __shfl(k, src, 64), b_pk = __shfl(pk, src, 64), b_prev = __shfl(prev, src, 64);
+            const uint32_t b_s = (uint32_t)__shfl(s, src, 64), b_w = (uint32_t)__shfl((int)w, src, 64);
+            uint64_t W = 0;
+            for (int32_t base = 0; base < b_k; base += 64) {
+                const int32_t i = base + lane;
+                if (i < b_k) W += pt_class_of(col[b_e0 + i], b_prev, sadj, b_pe0, b_pk, bias);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) W += (uint64_t)__shfl_xor((long long)W, off, 64);
+            const uint32_t hop_f = 0x80000000u + 256u * (uint32_t)PT_TRIALS + (uint32_t)h;
+            const uint64_t t = threshold(uniform53(seed, stream, b_s, b_w, hop_f), W);  // (every lane: the same words, no divergence)
+            uint64_t run = 0;
+            int32_t pick = -1;
+            for (int32_t base = 0; base < b_k; base += 64) {
+                const int32_t i = base + lane;
+                const int32_t x = i < b_k ? col[b_e0 + i] : -1;
+                const uint32_t c = i < b_k ? pt_class_of(x, b_prev, sadj, b_pe0, b_pk, bias) : 0u;
+                uint32_t inc = c;  // (at most 64 * 65536: 32 bits hold a chunk)
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t y = (uint32_t)__shfl_up((int)inc, off, 64);
+                    if (lane >= off) inc += y;
+                }
+                const uint64_t hit = __ballot(i < b_k && run + inc > t);
+                if (hit != 0ull) {
+                    pick = __shfl(x, __ffsll((unsigned long long)hit) - 1, 64);
+                    break;
+                }
+                run += (uint64_t)(uint32_t)__shfl((int)inc, 63, 64);
+            }
+            if (lane == src) nxt = pick;  // (t < W: a hit is certain)
+        }
+        if (alive) {
+            prev = cur;
+            pe0 = e0;
+            pk = k;
+            cur = nxt;
+            p[h] = cur;
+            len = h + 1;
+        }
+    }
+    if (valid) {
+        for (int h = len; h < walk_len; ++h) p[h] = -1;
+        path_len[g] = len;
+    }
 }
 
 // P5: rows of a walk = (1 + n_neg) * pairs of its path
@@ -201,6 +326,16 @@ int gg_pretrain_set_noise(gg_ctx *ctx, const uint32_t *weight) {
     return GG_OK;
 }
 
+int gg_pretrain_set_walk_bias(gg_ctx *ctx, uint32_t w_ret, uint32_t w_com, uint32_t w_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    for (uint32_t v : {w_ret, w_com, w_out})
+        GG_CHECK(ctx, v >= 1 && v <= 65536, GG_EINVAL, "gg_pretrain_set_walk_bias: weights must be in [1, 65536], got (%u, %u, %u)", w_ret, w_com, w_out);
+    ctx->pt_bias[0] = w_ret;
+    ctx->pt_bias[1] = w_com;
+    ctx->pt_bias[2] = w_out;
+    return GG_OK;
+}
+
 int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, int32_t walks_per_start, int32_t walk_len,
                         int32_t window, int32_t n_neg, uint64_t seed, uint32_t stream, int64_t *n_rows_out, int32_t *paths,
                         int32_t *path_len) {
@@ -219,6 +354,12 @@ int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, in
     const int64_t nw = (int64_t)n_starts * walks_per_start;
     GG_CHECK(ctx, nw <= 0x7fffffffll, GG_ECAPACITY, "gg_prepare_pretrain: %lld walks in one call", (long long)nw);
     GG_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t *wb = ctx->pt_bias;
+    const bool biased = !(wb[0] == wb[1] && wb[1] == wb[2]);  // equal weights are P2 itself: the uniform kernel, untouched
+    if (biased && nw > 0) {
+        const int rc = ensure_sorted_adjacency(ctx);
+        if (rc != GG_OK) return rc;
+    }
     ctx->d_rows = 0;
     if (nw > 0) {
         // rows of a walk that reaches its full length: the capacity rule of the row buffers
@@ -234,9 +375,15 @@ int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, in
             for (hipEvent_t &e : ctx->pt_ev) GG_HIP(ctx, hipEventCreate(&e));
         GG_HIP(ctx, hipMemcpyAsync(ctx->pt_starts.p, starts, sizeof(int32_t) * (size_t)n_starts, hipMemcpyHostToDevice, ctx->stream));
         if (timed) GG_HIP(ctx, hipEventRecord(ctx->pt_ev[0], ctx->stream));
-        hipLaunchKernelGGL(pt_walk_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->g_rowptr, ctx->g_col,
-                           ctx->pt_starts.as<int32_t>(), nw, walks_per_start, walk_len, seed, stream, ctx->pt_paths.as<int32_t>(),
-                           ctx->pt_len.as<int32_t>());
+        if (biased)
+            hipLaunchKernelGGL(pt_walk_bias_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->g_rowptr, ctx->g_col,
+                               ctx->topk_adj.as<int32_t>(), ctx->pt_starts.as<int32_t>(), nw, walks_per_start, walk_len, seed, stream,
+                               PtBias{wb[0], wb[1], wb[2], std::max(wb[0], std::max(wb[1], wb[2]))}, ctx->pt_paths.as<int32_t>(),
+                               ctx->pt_len.as<int32_t>());
+        else
+            hipLaunchKernelGGL(pt_walk_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->g_rowptr, ctx->g_col,
+                               ctx->pt_starts.as<int32_t>(), nw, walks_per_start, walk_len, seed, stream, ctx->pt_paths.as<int32_t>(),
+                               ctx->pt_len.as<int32_t>());
         if (timed) GG_HIP(ctx, hipEventRecord(ctx->pt_ev[1], ctx->stream));
         hipLaunchKernelGGL(pt_count_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->pt_len.as<int32_t>(), nw, window, n_neg,
                            ctx->pt_cnt.as<int32_t>());

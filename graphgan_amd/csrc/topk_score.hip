@@ -269,8 +269,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const u64 *part, int n_
 }  // namespace
 
 // The resident adjacency with every node's list sorted (binary search of the exclusion test); built on first use after
-// gg_set_graph_csr, which drops it.  The resident lists themselves stay in file order (the BFS trees depend on it).
-static int ensure_sorted_adjacency(gg_ctx *ctx) {
+// gg_set_graph_csr, which drops it.  The resident lists themselves stay in file order (the BFS trees depend on it).  Shared with
+// the biased pre-training walks (pretrain.hip: membership in the list of the previous node).
+int ensure_sorted_adjacency(gg_ctx *ctx) {
     if (ctx->topk_adj_valid) return GG_OK;
     const int n = ctx->n_node;
     std::vector<int32_t> s(ctx->h_col);
@@ -284,7 +285,7 @@ static int ensure_sorted_adjacency(gg_ctx *ctx) {
     for (auto &x : th) x.join();
     hipError_t e = ctx->topk_adj.reserve(sizeof(int32_t) * std::max<size_t>(s.size(), 1));
     if (e == hipSuccess && !s.empty()) e = hipMemcpy(ctx->topk_adj.p, s.data(), sizeof(int32_t) * s.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "gg_topk_scores: sorted adjacency (%lld entries): %s", (long long)s.size(), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "sorted adjacency (%lld entries): %s", (long long)s.size(), hipGetErrorString(e));
     ctx->topk_adj_valid = true;
     return GG_OK;
 }

@@ -361,8 +361,18 @@ class Engine:
         w = np.ascontiguousarray(w, dtype=np.uint32)
         self._ck(lib.gg_pretrain_set_noise(self._ctx, _ptr(w)))
 
+    def pretrain_set_walk_bias(self, w_ret, w_com, w_out):
+        """node2vec bias of the walks of ``prepare_pretrain`` (gg_pretrain_set_walk_bias; contract P2b): integer weights in
+        [1, 65536] of stepping back to the previous node, to a neighbour of it, and to any other neighbour.  Equal weights
+        are the uniform walk.  Kept across ``set_graph_csr``; ``pretrain.walk_bias(p, q)`` gives the weights of (p, q)."""
+        for name, val in (("w_ret", w_ret), ("w_com", w_com), ("w_out", w_out)):
+            if isinstance(val, (bool, np.bool_)) or not isinstance(val, (int, np.integer)) or not 1 <= int(val) <= 65536:
+                raise ValueError("pretrain_set_walk_bias: %s must be an integer in [1, 65536], got %r" % (name, val))
+        self._ck(lib.gg_pretrain_set_walk_bias(self._ctx, int(w_ret), int(w_com), int(w_out)))
+
     def prepare_pretrain(self, starts, walks_per_start, walk_len, window, n_neg, seed, stream, fetch=False):
-        """Skip-gram rows from uniform random walks (gg_prepare_pretrain; contract P1-P5 in include/graphgan_hip.h):
+        """Skip-gram rows from random walks -- uniform, or biased after ``pretrain_set_walk_bias`` -- (gg_prepare_pretrain;
+        contract P1-P5 in include/graphgan_hip.h):
         ``walks_per_start`` walks of ``walk_len`` nodes from every node of ``starts``, window pairs as positives, ``n_neg``
         negatives per pair.  The rows replace the resident discriminator rows (``get_d_data`` / ``d_pass``).  Returns the row
         count, or with ``fetch`` (rows, paths int32 [walks, walk_len] with -1 behind a walk's end, path_len int32 [walks])."""

@@ -89,8 +89,8 @@ class GraphGAN(object):
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
         # reference never seeds it (Q5) -- seeding it here makes the whole run reproducible
         np.random.seed(self.seed)
-        # engine_pretrain: a missing pre-trained file is produced from the edge list (skip-gram on uniform random walks, on the
-        # device) and written in the reference's .emb text; the unchanged read below then finds it.  Off by default: a missing
+        # engine_pretrain: a missing pre-trained file is produced from the edge list (skip-gram on uniform or node2vec --
+        # engine_pretrain_p / _q -- random walks, on the device) and written in the reference's .emb text; the unchanged read below then finds it.  Off by default: a missing
         # file raises as in the reference.  With replicas rank 0 writes, the others wait for the file.
         if _cfg(cfg, "engine_pretrain", False):
             from graphgan_amd import pretrain as _pretrain

@@ -1,4 +1,4 @@
-"""Skip-gram pre-training of the initial embeddings from uniform random walks, on the device.
+"""Skip-gram pre-training of the initial embeddings from uniform or node2vec (p, q) biased random walks, on the device.
 
 The reference starts from ``pre_train/*.emb`` files of an external DeepWalk / node2vec run (config.py:33-34); this module
 produces such a table from the edge list alone.  ``Engine.prepare_pretrain`` writes the (center, neighbor, label) rows of
@@ -6,7 +6,7 @@ the walks' window pairs and their negative samples into the resident discriminat
 cross-entropy on one table -- trains on them: one-table skip-gram with negative sampling.  All sampling and arithmetic run
 in ``libgraphgan_hip.so``.
 
-    python -m graphgan_amd.pretrain --train <edge list> [--test <edge list>] --out <file.emb> [--n-emb 50] ...
+    python -m graphgan_amd.pretrain --train <edge list> [--test <edge list>] --out <file.emb> [--n-emb 50] [--p 1 --q 1] ...
 """
 from __future__ import annotations
 
@@ -41,6 +41,19 @@ def noise_weights(rowptr):
     return np.round(16.0 * np.maximum(deg, 1).astype(np.float64) ** 0.75).astype(np.uint32)
 
 
+BIAS_SCALE = 4096  # weight of the largest of (1/p, 1, 1/q)
+
+
+def walk_bias(p, q):
+    """Integer walk weights (w_ret, w_com, w_out) of node2vec's return parameter ``p`` and in-out parameter ``q``, each in
+    [1/16, 16]: max(1, round(4096 * v / max(v))) for v = (1/p, 1, 1/q).  p = q = 1 gives equal weights, the uniform walk."""
+    p, q = float(p), float(q)
+    if not (1.0 / 16 <= p <= 16.0 and 1.0 / 16 <= q <= 16.0):
+        raise ValueError("walk_bias: p and q must lie in [1/16, 16], got p = %r, q = %r" % (p, q))
+    v = (1.0 / p, 1.0, 1.0 / q)
+    return tuple(max(1, int(round(BIAS_SCALE * x / max(v)))) for x in v)
+
+
 def init_table(n_node, n_emb, seed):
     """word2vec's initialisation (U(-0.5, 0.5) / d) from RandomState(seed)."""
     return ((np.random.RandomState(seed).rand(n_node, n_emb) - 0.5) / n_emb).astype(np.float32)
@@ -59,11 +72,13 @@ def pretrain(cfg, n_node, rowptr, col):
     walks, length = int(_cfg(cfg, "engine_pretrain_walks")), int(_cfg(cfg, "engine_pretrain_len"))
     window, n_neg = int(_cfg(cfg, "engine_pretrain_window")), int(_cfg(cfg, "engine_pretrain_neg"))
     batch = int(_cfg(cfg, "engine_pretrain_batch"))
+    bias = walk_bias(_cfg(cfg, "engine_pretrain_p"), _cfg(cfg, "engine_pretrain_q"))
     init = init_table(n_node, d, seed)
     eng = _engine.Engine(init, init, lr_dis=float(_cfg(cfg, "engine_pretrain_lr")), lambda_dis=float(_cfg(cfg, "lambda_dis")),
                          optimizer=_lib.GG_OPT_ADAM_LAZY, device=int(_cfg(cfg, "engine_device")))
     try:
         eng.set_graph_csr(rowptr, col)
+        eng.pretrain_set_walk_bias(*bias)
         eng.pretrain_set_noise(noise_weights(rowptr))
         rng = np.random.RandomState(seed)
         batches = start_batches(n_node, rows_bound(walks, length, window, n_neg), int(_cfg(cfg, "engine_pretrain_rows_per_call")))
@@ -96,7 +111,7 @@ def ensure_pretrained(cfg, n_node, rowptr, col):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="skip-gram pre-training from uniform random walks -> .emb")
+    ap = argparse.ArgumentParser(description="skip-gram pre-training from uniform or node2vec (p, q) random walks -> .emb")
     ap.add_argument("--train", required=True)
     ap.add_argument("--test", default="")
     ap.add_argument("--out", required=True)
@@ -106,9 +121,11 @@ def main(argv=None):
     for k in ("walks", "len", "window", "neg", "epochs", "batch", "rows_per_call"):
         ap.add_argument("--" + k.replace("_", "-"), type=int, default=getattr(_default_config, "engine_pretrain_" + k))
     ap.add_argument("--lr", type=float, default=_default_config.engine_pretrain_lr)
+    ap.add_argument("--p", type=float, default=_default_config.engine_pretrain_p, help="node2vec return parameter, in [1/16, 16]")
+    ap.add_argument("--q", type=float, default=_default_config.engine_pretrain_q, help="node2vec in-out parameter, in [1/16, 16]")
     a = ap.parse_args(argv)
     cfg = argparse.Namespace(n_emb=a.n_emb, engine_seed=a.seed, engine_device=a.device, lambda_dis=_default_config.lambda_dis,
-                             engine_pretrain_lr=a.lr, **{"engine_pretrain_" + k: getattr(a, k) for k in
+                             engine_pretrain_lr=a.lr, engine_pretrain_p=a.p, engine_pretrain_q=a.q, **{"engine_pretrain_" + k: getattr(a, k) for k in
                                                          ("walks", "len", "window", "neg", "epochs", "batch", "rows_per_call")})
     n_node, rowptr, col = _engine.read_edges_csr(a.train, a.test)
     emb = pretrain(cfg, n_node, rowptr, col)

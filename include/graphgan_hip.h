@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GG_ABI_VERSION 9  /* (gg_pretrain_set_noise / gg_prepare_pretrain are ADDITIVE: two new symbols, nothing existing changes, the number stays) gg_graph_softmax; 8: gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
+#define GG_ABI_VERSION 9  /* (gg_pretrain_set_noise / gg_prepare_pretrain / gg_pretrain_set_walk_bias are ADDITIVE: new symbols, nothing existing changes, the number stays) gg_graph_softmax; 8: gg_topk_scores; round 6: lazy trees (gg_set_tree_mode, gg_lazy_stats, gg_get_lazy_trees); round 5: gg_comm_stats_ex; round 4: epoch over root batches (gg_epoch_*, gg_q3_*); round 3: gg_counters extended, gg_prepare_g_begin */
 
 enum {
     GG_OK = 0,
@@ -369,6 +369,23 @@ int gg_graph_softmax(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t
  *   P2 walk           start node s, walk w in [0, walks_per_start): path[0] = s; for h = 1 .. walk_len - 1 with cur = path[h - 1],
  *                     k = deg(cur): k == 0 ends the walk (path_len = h), else path[h] = col[rowptr[cur] + t(k)] drawn with hop = h.
  *                     Walks are stored in the order (start index, w); entries behind path_len are -1.
+ *   P2b biased walk   (node2vec; replaces P2 while gg_pretrain_set_walk_bias holds unequal weights).  Walk bias: three integers
+ *                     (w_ret, w_com, w_out), each in [1, 65536], M = the largest.  CLASS of a candidate x at hop h, with
+ *                     prev = path[h - 2], tested in this order: x == prev -> w_ret; x occurs in adj(prev), the resident list of
+ *                     prev exactly as handed to gg_set_graph_csr (duplicates are fine, a directed CSR stays well defined) -> w_com;
+ *                     otherwise -> w_out.  Hop h with cur = path[h - 1], k = deg(cur), e0 = rowptr[cur]: k == 0 ends the walk
+ *                     as in P2.  If h == 1, or k == 1, or w_ret == w_com == w_out: exactly P2 (one draw with hop word h,
+ *                     path[h] = col[e0 + t(k)]).  Otherwise trials r = 0 .. R - 1, R = 32: the candidate
+ *                     x_r = col[e0 + threshold(m_c(r), k)] is drawn from the list in FILE order, m_c(0) = uniform53(seed, stream,
+ *                     start, w, hop = h) and m_c(r >= 1) uses hop word 2^31 + 256 r + h; it is accepted iff class(x_r) == M or
+ *                     threshold(m_a(r), M) < class(x_r), where m_a(r) uses hop word 2^30 + 256 r + h; the first accepted
+ *                     candidate is path[h].  If all R trials are rejected, one exact draw: W = sum of class(col[e]) over the list
+ *                     of cur in file order, t = threshold(m_f, W) with hop word 2^31 + 256 R + h for m_f, and path[h] is the first
+ *                     list entry whose inclusive prefix sum of class weights exceeds t.
+ *                     The hop words are disjoint from every P2 / P4 draw: h <= 255 and the negatives' hop words stay below 2^30
+ *                     (walk_len + pairs * n_neg <= 256 + 8192 * 64).  Consequences: every step has exactly the node2vec law
+ *                     class(x) / W per list entry (rejection and the exact draw both realise it); equal weights reproduce P2 BIT
+ *                     FOR BIT; draws are keyed by (start, w, hop word) only, so any decomposition gives the same paths.
  *   P3 pairs          over the WHOLE path of length l (there is no back-step entry to drop, unlike get_node_pairs_from_path,
  *                     graph_gan.py:272-291): for i ascending and j in [max(i - window, 0), min(i + window, l - 1)] ascending, j != i,
  *                     pair number p is (path[i], path[j]).
@@ -382,6 +399,11 @@ int gg_graph_softmax(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t
  *   limits            1 <= walk_len <= 256, 1 <= window <= 16, 0 <= n_neg <= 64, walks_per_start >= 1; repeated start nodes are
  *                     allowed and give identical walks.
  * gg_pretrain_set_noise: weight[n_node] (copied; all zero: GG_EINVAL) or NULL = uniform.  gg_set_graph_csr drops the table.
+ * gg_pretrain_set_walk_bias: the walk bias of P2b, held in the context (default (1, 1, 1)) and KEPT across gg_set_graph_csr -- it
+ * does not depend on the graph, unlike the noise table.  A weight of 0 or above 65536: GG_EINVAL (no graph needed).  With equal
+ * weights gg_prepare_pretrain launches the uniform walk kernel exactly as before; with unequal weights the biased kernel, which
+ * tests membership by binary search in a per-node SORTED copy of the lists (built on first use after gg_set_graph_csr, shared
+ * with gg_topk_scores' exclusion; candidates are still drawn from the file-order lists), then the same count / scan / fill.
  * gg_prepare_pretrain: needs gg_set_graph_csr.  REPLACES the resident discriminator rows exactly as a gg_prepare_d call does
  * (gg_get_d_data and gg_d_pass then work on them unchanged); *n_rows_out = their number; paths [n_starts * walks_per_start *
  * walk_len] and path_len [n_starts * walks_per_start] may be NULL.  It has path buffers of its own and neither reads nor writes
@@ -391,8 +413,9 @@ int gg_graph_softmax(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t
  * GG_EINVAL: no graph, a limit violated, a start out of range, an attached communicator (single rank only), a call between
  * gg_epoch_begin(reset_d) / gg_epoch_add(do_d) and the matching gg_epoch_commit(1).  GG_ECAPACITY: more than 2^31 - 1 rows (or
  * walks) in one call.  With profiling cadence 1 (gg_set_profiling) gg_counters.last_kernel_ms = HIP-event time of the row (fill)
- * kernel and walk_kernel_ms / walk_launches also count this call's walk kernel. */
+ * kernel and walk_kernel_ms / walk_launches also count this call's walk kernel (the uniform or the biased one). */
 int gg_pretrain_set_noise(gg_ctx *ctx, const uint32_t *weight /*[n_node] or NULL = uniform*/);
+int gg_pretrain_set_walk_bias(gg_ctx *ctx, uint32_t w_ret, uint32_t w_com, uint32_t w_out /*each in [1, 65536]*/);
 int gg_prepare_pretrain(gg_ctx *ctx, const int32_t *starts, int32_t n_starts, int32_t walks_per_start, int32_t walk_len,
                         int32_t window, int32_t n_neg, uint64_t seed, uint32_t stream, int64_t *n_rows_out,
                         int32_t *paths /*[n_starts*walks_per_start*walk_len] or NULL*/, int32_t *path_len /*or NULL*/);
