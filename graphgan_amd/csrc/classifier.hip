@@ -325,42 +325,55 @@ __global__ __launch_bounds__(256) void nc_adam_kernel(float *theta, float *mom, 
     theta[j] -= lr * (mj / c1) / (sqrtf(vj / c2) + 1e-8f);
 }
 
-// nc_ml_predict_kernel -- one wavefront per row at a time, W and the row in LDS as in nc_predict_kernel below.  Lane c holds
-// the logits of classes c and c + 64 and publishes them to LDS (zs); every lane then counts, over all C published logits (one
-// broadcast read each), the classes that come before its own in the total order (logit descending, class ascending): the rank.
-// A class is selected when rank < k[row] (k given) or z > 0 (k NULL).  Two ballots give the four mask words; lane j stores word j.
+// The front end of both prediction kernels.  One wavefront per row at a time: W in LDS ([C][ld + 1], zero padded), the row in
+// LDS, lane c (and c + 64) the class's dot product.  What a kernel does with its logits is its own tail.
+__device__ __forceinline__ void nc_stage_w(float *Ws, const float *W, int C, int d, int ld) {
+    for (int i = threadIdx.x; i < C * ld; i += 256) {
+        const int c = i / ld, kk = i - c * ld;
+        Ws[c * (ld + 1) + kk] = kk < d ? W[(int64_t)c * d + kk] : 0.f;
+    }
+    __syncthreads();
+}
+
+// the wavefront's LDS writes (the staged row; a kernel's published logits) become visible to its other lanes; also behind the
+// last read of a row, before the next one overwrites it
+__device__ __forceinline__ void nc_wave_sync() {
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+}
+
+__device__ __forceinline__ void nc_stage_row(float *xs, const float *x, int ld, int lane) {
+    for (int kk = lane; kk < ld; kk += 64) xs[kk] = x[kk];
+    nc_wave_sync();
+}
+
+// z[c] = sum_kk W[c][kk] x[kk] (kk ascending from 0: the order is part of the result) + b[c] of row `row`, stored to
+// logits [m][C] if given
+__device__ __forceinline__ float nc_logit(const float *Ws, const float *xs, int ld, const float *b, int c, float *logits, int64_t row, int C) {
+    const float *w = Ws + c * (ld + 1);
+    float z = 0.f;
+    for (int kk = 0; kk < ld; ++kk) z += w[kk] * xs[kk];
+    z += b[c];
+    if (logits) logits[row * C + c] = z;
+    return z;
+}
+
+// nc_ml_predict_kernel -- lane c holds the logits of classes c and c + 64 and publishes them to LDS (zs); every lane then
+// counts, over all C published logits (one broadcast read each), the classes that come before its own in the total order
+// (logit descending, class ascending): the rank.  A class is selected when rank < k[row] (k given) or z > 0 (k NULL).  Two
+// ballots give the four mask words; lane j stores word j.
 __global__ __launch_bounds__(256) void nc_ml_predict_kernel(const float *E, int ld, int d, const int32_t *nodes, int64_t m, int C, const float *W,
                                                            const float *b, const int32_t *k, uint32_t *pred_bits, float *logits) {
     extern __shared__ float nc_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, WS = ld + 1, CW = (C + 31) >> 5;
-    float *Ws = nc_lds, *xs = Ws + C * WS + wv * ld, *zs = Ws + C * WS + 4 * ld + wv * NC_MAX_C;
-    for (int i = tid; i < C * ld; i += 256) {
-        const int c = i / ld, kk = i - c * ld;
-        Ws[c * WS + kk] = kk < d ? W[(int64_t)c * d + kk] : 0.f;
-    }
-    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, CW = (C + 31) >> 5;
+    float *Ws = nc_lds, *xs = Ws + C * (ld + 1) + wv * ld, *zs = Ws + C * (ld + 1) + 4 * ld + wv * NC_MAX_C;
+    nc_stage_w(Ws, W, C, d, ld);
     for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < m; row += (int64_t)gridDim.x * 4) {
-        const float *x = E + (int64_t)nodes[row] * ld;
-        for (int kk = lane; kk < ld; kk += 64) xs[kk] = x[kk];
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
+        nc_stage_row(xs, E + (int64_t)nodes[row] * ld, ld, lane);
         float z0 = 0.f, z1 = 0.f;
-        if (lane < C) {
-            const float *w = Ws + lane * WS;
-            for (int kk = 0; kk < ld; ++kk) z0 += w[kk] * xs[kk];
-            z0 += b[lane];
-            if (logits) logits[row * C + lane] = z0;
-            zs[lane] = z0;
-        }
-        if (lane + 64 < C) {
-            const float *w = Ws + (lane + 64) * WS;
-            for (int kk = 0; kk < ld; ++kk) z1 += w[kk] * xs[kk];
-            z1 += b[lane + 64];
-            if (logits) logits[row * C + lane + 64] = z1;
-            zs[lane + 64] = z1;
-        }
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
+        if (lane < C) zs[lane] = z0 = nc_logit(Ws, xs, ld, b, lane, logits, row, C);
+        if (lane + 64 < C) zs[lane + 64] = z1 = nc_logit(Ws, xs, ld, b, lane + 64, logits, row, C);
+        nc_wave_sync();
         bool sel0, sel1;
         if (k) {
             int rank0 = 0, rank1 = 0;
@@ -378,36 +391,23 @@ __global__ __launch_bounds__(256) void nc_ml_predict_kernel(const float *E, int 
         }
         const unsigned long long m0 = __ballot(sel0), m1 = __ballot(sel1);  // classes 0 .. 63, 64 .. 127
         if (lane < CW) pred_bits[row * CW + lane] = (uint32_t)((lane < 2 ? m0 : m1) >> (32 * (lane & 1)));
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
+        nc_wave_sync();
     }
 }
 
-// One wavefront per row at a time: W in LDS ([C][ld + 1], zero padded), the row in LDS, lane c (and c + 64) the class's dot
-// product; argmax over (logit descending, class ascending) by a butterfly.
+// nc_predict_kernel -- argmax over (logit descending, class ascending) by a butterfly.
 __global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld, int d, const int32_t *nodes, int64_t m, int C, const float *W,
                                                         const float *b, int32_t *pred, float *logits) {
     extern __shared__ float nc_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, WS = ld + 1;
-    float *Ws = nc_lds, *xs = Ws + C * WS + wv * ld;
-    for (int i = tid; i < C * ld; i += 256) {
-        const int c = i / ld, k = i - c * ld;
-        Ws[c * WS + k] = k < d ? W[(int64_t)c * d + k] : 0.f;
-    }
-    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float *Ws = nc_lds, *xs = Ws + C * (ld + 1) + wv * ld;
+    nc_stage_w(Ws, W, C, d, ld);
     for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < m; row += (int64_t)gridDim.x * 4) {
-        const float *x = E + (int64_t)nodes[row] * ld;
-        for (int k = lane; k < ld; k += 64) xs[k] = x[k];
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
+        nc_stage_row(xs, E + (int64_t)nodes[row] * ld, ld, lane);
         float best = -INFINITY;
         int bc = 0x7fffffff;
         for (int c = lane; c < C; c += 64) {
-            float z = 0.f;
-            const float *w = Ws + c * WS;
-            for (int k = 0; k < ld; ++k) z += w[k] * xs[k];
-            z += b[c];
-            if (logits) logits[row * C + c] = z;
+            const float z = nc_logit(Ws, xs, ld, b, c, logits, row, C);
             if (z > best || bc == 0x7fffffff) {  // (the lane's classes ascend: a later equal logit does not replace)
                 best = z;
                 bc = c;
@@ -423,8 +423,7 @@ __global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld,
             }
         }
         if (lane == 0) pred[row] = bc;
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
+        nc_wave_sync();
     }
 }
 
@@ -455,10 +454,25 @@ SweepPlan sweep_plan(int64_t m, int C, int ld, bool ml) {
     return p;
 }
 
-// device state of one call
+// A device allocation that lives as long as one call: released when the call returns, on every path -- behind the stream
+// synchronisation, or behind the HIP call that failed.
+struct ScopedBuf : DevBuf {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf &) = delete;
+    ScopedBuf &operator=(const ScopedBuf &) = delete;
+    ~ScopedBuf() { release(); }
+};
+
+// A HIP call of the entry point `fn`: its failure ends the call with the entry point's name in the error text.
+#define NC_HIP(call)                                                                           \
+    do {                                                                                       \
+        const hipError_t e__ = (call);                                                         \
+        if (e__ != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e__)); \
+    } while (0)
+
+// device state of a fit or loss-and-gradient call
 struct Fit {
-    DevBuf nodes, labels, theta, mom, var, grad, part, loss;
-    void release() { nodes.release(); labels.release(); theta.release(); mom.release(); var.release(); grad.release(); part.release(); loss.release(); }
+    ScopedBuf nodes, labels, theta, mom, var, grad, part, loss;
 };
 
 int check_common(gg_ctx *ctx, const char *fn, int which, const int32_t *nodes, int64_t m, int n_class) {
@@ -493,22 +507,29 @@ int check_label_bits(gg_ctx *ctx, const char *fn, const uint32_t *bits, int64_t 
     return GG_OK;
 }
 
+// the rows and the parameters of a call to the device: nodes int32 [m], theta = (W [C, d], b [C]).  The caller has reserved both,
+// with its other buffers: every allocation of a call comes before its first copy.
+hipError_t upload_nodes_theta(gg_ctx *ctx, DevBuf &d_nodes, DevBuf &d_theta, const int32_t *nodes, int64_t m, int C, const float *W, const float *b) {
+    const size_t cd = (size_t)C * ctx->n_emb;
+    hipError_t e = hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
+    return e;
+}
+
 // nodes, labels (one int32 class per row, or with `ml` the mask words uint32 [m][ceil(C / 32)]), theta = (W, b) on the device;
 // the stage and the gradient
 hipError_t fit_upload(gg_ctx *ctx, Fit &f, const SweepPlan &p, bool ml, const int32_t *nodes, const void *labels, int64_t m, int C, const float *W,
                       const float *b) {
-    const int d = ctx->n_emb;
-    const size_t cd = (size_t)C * d, n_par = cd + C;
+    const size_t n_par = (size_t)C * ctx->n_emb + C;
     const size_t label_bytes = sizeof(int32_t) * (size_t)m * (ml ? cdiv(C, 32) : 1);
     hipError_t e = f.nodes.reserve(sizeof(int32_t) * m);
     if (e == hipSuccess) e = f.labels.reserve(label_bytes);
     if (e == hipSuccess) e = f.theta.reserve(sizeof(float) * n_par);
     if (e == hipSuccess) e = f.grad.reserve(sizeof(float) * (n_par + 1));
     if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (n_par + 2) * p.grid);
-    if (e == hipSuccess) e = hipMemcpyAsync(f.nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = upload_nodes_theta(ctx, f.nodes, f.theta, nodes, m, C, W, b);
     if (e == hipSuccess) e = hipMemcpyAsync(f.labels.p, labels, label_bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && p.lds > 48 * 1024) e = hipFuncSetAttribute((const void *)p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     return e;
 }
@@ -542,17 +563,13 @@ int lossgrad_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t
     const size_t cd = (size_t)C * ctx->n_emb;
     const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    hipError_t e = fit_upload(ctx, f, p, ml, nodes, labels, m, C, W, b);
-    if (e == hipSuccess) {
-        enqueue_lossgrad(ctx, f, p, which, m, C, l2, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(gW_out, f.grad.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(gb_out, f.grad.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    f.release();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    NC_HIP(fit_upload(ctx, f, p, ml, nodes, labels, m, C, W, b));
+    enqueue_lossgrad(ctx, f, p, which, m, C, l2, nullptr);
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(gW_out, f.grad.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(gb_out, f.grad.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 
@@ -571,34 +588,71 @@ int fit_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t *nod
     const size_t cd = (size_t)C * ctx->n_emb, n_par = cd + C;
     const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    hipError_t e = fit_upload(ctx, f, p, ml, nodes, labels, m, C, W_inout, b_inout);
-    if (e == hipSuccess) e = f.mom.reserve(sizeof(float) * n_par);
-    if (e == hipSuccess) e = f.var.reserve(sizeof(float) * n_par);
-    if (e == hipSuccess) e = f.loss.reserve(sizeof(float) * iters);
-    if (e == hipSuccess) e = hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream);
-    if (e == hipSuccess) {
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        double b1p = 1.0, b2p = 1.0;
-        for (int t = 0; t < iters; ++t) {
-            b1p *= 0.9;
-            b2p *= 0.999;
-            enqueue_lossgrad(ctx, f, p, which, m, C, l2, f.loss.as<float>() + t);
-            hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
-                               f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
-        }
-        (void)hipEventRecord(ctx->ev1, ctx->stream);
-        e = hipGetLastError();
+    NC_HIP(fit_upload(ctx, f, p, ml, nodes, labels, m, C, W_inout, b_inout));
+    NC_HIP(f.mom.reserve(sizeof(float) * n_par));
+    NC_HIP(f.var.reserve(sizeof(float) * n_par));
+    NC_HIP(f.loss.reserve(sizeof(float) * iters));
+    NC_HIP(hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream));
+    NC_HIP(hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream));
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    double b1p = 1.0, b2p = 1.0;
+    for (int t = 0; t < iters; ++t) {
+        b1p *= 0.9;
+        b2p *= 0.999;
+        enqueue_lossgrad(ctx, f, p, which, m, C, l2, f.loss.as<float>() + t);
+        hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
+                           f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(W_inout, f.theta.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b_inout, f.theta.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && loss_out) e = hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(W_inout, f.theta.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(b_inout, f.theta.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream));
+    if (loss_out) NC_HIP(hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    f.release();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     if (ms_out) *ms_out = ms;
+    return GG_OK;
+}
+
+// gg_classifier_predict / gg_classifier_ml_predict: `pred_out` is int32 [m] (the argmax), or with `ml` the mask words uint32
+// [m][ceil(C / 32)] of the first k[i] classes (k given) or of the classes with a positive logit (k NULL; `k` is the ml form's alone)
+int predict_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
+                 const int32_t *k, void *pred_out, float *logits_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_common(ctx, fn, which, nodes, m, n_class)) return rc;
+    GG_CHECK(ctx, W && b && pred_out, GG_EINVAL, "%s: W, b and %s must not be NULL", fn, ml ? "pred_bits" : "pred_out");
+    if (k)
+        for (int64_t i = 0; i < m; ++i)
+            GG_CHECK(ctx, k[i] >= 0 && k[i] <= n_class, GG_EINVAL, "%s: k = %d (row %lld) outside [0, n_class = %d]", fn, k[i], (long long)i, n_class);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int C = n_class, d = ctx->n_emb, ld = ctx->ld;
+    const size_t cd = (size_t)C * d, pred_bytes = sizeof(int32_t) * (size_t)m * (ml ? cdiv(C, 32) : 1), logit_bytes = sizeof(float) * (size_t)m * C;
+    // W [C][ld + 1], a row per wavefront, and the ml form's published logits per wavefront
+    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld + (ml ? 4 * (size_t)NC_MAX_C : 0));
+    const void *kernel = ml ? (const void *)nc_ml_predict_kernel : (const void *)nc_predict_kernel;
+    ScopedBuf d_nodes, d_theta, d_k, d_pred, d_logits;
+    NC_HIP(d_nodes.reserve(sizeof(int32_t) * m));
+    NC_HIP(d_theta.reserve(sizeof(float) * (cd + C)));
+    if (k) NC_HIP(d_k.reserve(sizeof(int32_t) * m));
+    NC_HIP(d_pred.reserve(pred_bytes));
+    if (logits_out) NC_HIP(d_logits.reserve(logit_bytes));
+    NC_HIP(upload_nodes_theta(ctx, d_nodes, d_theta, nodes, m, C, W, b));
+    if (k) NC_HIP(hipMemcpyAsync(d_k.p, k, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+    if (lds > 48 * 1024) NC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((unsigned)std::min<int64_t>(1024, (m + 3) / 4));
+    const float *E = ctx->model[which].E, *dW = d_theta.as<float>(), *db = dW + cd;
+    if (ml) {
+        hipLaunchKernelGGL(nc_ml_predict_kernel, grid, dim3(256), lds, ctx->stream, E, ld, d, d_nodes.as<int32_t>(), m, C, dW, db, d_k.as<int32_t>(),
+                           d_pred.as<uint32_t>(), d_logits.as<float>());
+    } else {
+        hipLaunchKernelGGL(nc_predict_kernel, grid, dim3(256), lds, ctx->stream, E, ld, d, d_nodes.as<int32_t>(), m, C, dW, db, d_pred.as<int32_t>(),
+                           d_logits.as<float>());
+    }
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(pred_out, d_pred.p, pred_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_out) NC_HIP(hipMemcpyAsync(logits_out, d_logits.p, logit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 
@@ -629,77 +683,13 @@ extern "C" int gg_classifier_ml_fit(gg_ctx *ctx, int which, const int32_t *nodes
     return fit_call(ctx, "gg_classifier_ml_fit", true, which, nodes, label_bits, m, n_class, iters, lr, l2, W_inout, b_inout, loss_out, ms_out);
 }
 
-// gg_classifier_predict: see include/graphgan_hip.h.
+// gg_classifier_predict, gg_classifier_ml_predict: see include/graphgan_hip.h.
 extern "C" int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
                                      int32_t *pred_out, float *logits_out) {
-    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    if (const int rc = check_common(ctx, "gg_classifier_predict", which, nodes, m, n_class)) return rc;
-    GG_CHECK(ctx, W && b && pred_out, GG_EINVAL, "gg_classifier_predict: W, b and pred_out must not be NULL");
-    GG_HIP(ctx, hipSetDevice(ctx->device));
-    const int C = n_class, d = ctx->n_emb, ld = ctx->ld;
-    const size_t cd = (size_t)C * d;
-    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld);
-    DevBuf d_nodes, d_theta, d_pred, d_logits;
-    auto rel = [&]() { d_nodes.release(); d_theta.release(); d_pred.release(); d_logits.release(); };
-    hipError_t e = d_nodes.reserve(sizeof(int32_t) * m);
-    if (e == hipSuccess) e = d_theta.reserve(sizeof(float) * (cd + C));
-    if (e == hipSuccess) e = d_pred.reserve(sizeof(int32_t) * m);
-    if (e == hipSuccess && logits_out) e = d_logits.reserve(sizeof(float) * (size_t)m * C);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute((const void *)nc_predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-        const int grid = (int)std::min<int64_t>(1024, (m + 3) / 4);
-        hipLaunchKernelGGL(nc_predict_kernel, dim3(grid), dim3(256), lds, ctx->stream, ctx->model[which].E, ld, d, d_nodes.as<int32_t>(), m, C,
-                           d_theta.as<float>(), d_theta.as<float>() + cd, d_pred.as<int32_t>(), logits_out ? d_logits.as<float>() : nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(pred_out, d_pred.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && logits_out) e = hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m * C, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    rel();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_predict: %s", hipGetErrorString(e));
-    return GG_OK;
+    return predict_call(ctx, "gg_classifier_predict", false, which, nodes, m, n_class, W, b, nullptr, pred_out, logits_out);
 }
 
-// gg_classifier_ml_predict: see include/graphgan_hip.h.
 extern "C" int gg_classifier_ml_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
                                         const int32_t *k, uint32_t *pred_bits, float *logits_out) {
-    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    if (const int rc = check_common(ctx, "gg_classifier_ml_predict", which, nodes, m, n_class)) return rc;
-    GG_CHECK(ctx, W && b && pred_bits, GG_EINVAL, "gg_classifier_ml_predict: W, b and pred_bits must not be NULL");
-    if (k)
-        for (int64_t i = 0; i < m; ++i)
-            GG_CHECK(ctx, k[i] >= 0 && k[i] <= n_class, GG_EINVAL, "gg_classifier_ml_predict: k = %d (row %lld) outside [0, n_class = %d]", k[i],
-                     (long long)i, n_class);
-    GG_HIP(ctx, hipSetDevice(ctx->device));
-    const int C = n_class, d = ctx->n_emb, ld = ctx->ld, CW = cdiv(C, 32);
-    const size_t cd = (size_t)C * d;
-    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld + 4 * (size_t)NC_MAX_C);
-    DevBuf d_nodes, d_theta, d_k, d_pred, d_logits;
-    auto rel = [&]() { d_nodes.release(); d_theta.release(); d_k.release(); d_pred.release(); d_logits.release(); };
-    hipError_t e = d_nodes.reserve(sizeof(int32_t) * m);
-    if (e == hipSuccess) e = d_theta.reserve(sizeof(float) * (cd + C));
-    if (e == hipSuccess && k) e = d_k.reserve(sizeof(int32_t) * m);
-    if (e == hipSuccess) e = d_pred.reserve(sizeof(uint32_t) * (size_t)m * CW);
-    if (e == hipSuccess && logits_out) e = d_logits.reserve(sizeof(float) * (size_t)m * C);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && k) e = hipMemcpyAsync(d_k.p, k, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.p, W, sizeof(float) * cd, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_theta.as<float>() + cd, b, sizeof(float) * C, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute((const void *)nc_ml_predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-        const int grid = (int)std::min<int64_t>(1024, (m + 3) / 4);
-        hipLaunchKernelGGL(nc_ml_predict_kernel, dim3(grid), dim3(256), lds, ctx->stream, ctx->model[which].E, ld, d, d_nodes.as<int32_t>(), m, C,
-                           d_theta.as<float>(), d_theta.as<float>() + cd, k ? d_k.as<int32_t>() : nullptr, d_pred.as<uint32_t>(),
-                           logits_out ? d_logits.as<float>() : nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(pred_bits, d_pred.p, sizeof(uint32_t) * (size_t)m * CW, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && logits_out) e = hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m * C, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    rel();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_classifier_ml_predict: %s", hipGetErrorString(e));
-    return GG_OK;
+    return predict_call(ctx, "gg_classifier_ml_predict", true, which, nodes, m, n_class, W, b, k, pred_bits, logits_out);
 }

@@ -606,43 +606,50 @@ class Engine:
             raise ValueError("%s: W must be [n_class, %d] and b [n_class], got %r and %r" % (fn, self.n_emb, W.shape, b.shape))
         return W, b
 
+    def _nc_lossgrad(self, cfunc, nodes_a, labels_dev, which, l2, W, b):
+        """the loss-and-gradient call of either label form: ``labels_dev`` is what ``cfunc`` reads (int32 classes or mask words)"""
+        loss = np.zeros(1, dtype=np.float32)
+        gW = np.empty_like(W)
+        gb = np.empty_like(b)
+        self._ck(cfunc(self._ctx, which, _ptr(nodes_a), _ptr(labels_dev), len(nodes_a), int(W.shape[0]), _ptr(W), _ptr(b), float(l2),
+                       _ptr(loss), _ptr(gW), _ptr(gb)))
+        return dict(loss=float(loss[0]), gW=gW, gb=gb)
+
+    def _nc_fit(self, fn, cfunc, nodes_a, labels_dev, n_class, which, iters, lr, l2, W, b):
+        """the fit call of either label form (``fn``: the public method, for the error texts; ``labels_dev`` as in _nc_lossgrad)"""
+        C = int(n_class)
+        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
+            raise ValueError("%s: iters must be an integer >= 1, got %r" % (fn, iters))
+        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
+            raise ValueError("%s: lr must be > 0 and l2 >= 0, got %r and %r" % (fn, lr, l2))
+        if (W is None) != (b is None):
+            raise ValueError("%s: give both W and b, or neither" % fn)
+        if W is None:
+            W, b = np.zeros((C, self.n_emb), dtype=np.float32), np.zeros(C, dtype=np.float32)
+        else:
+            W, b = self._nc_params(fn, W, b)
+            if W.shape[0] != C:
+                raise ValueError("%s: W has %d rows, n_class is %d" % (fn, W.shape[0], C))
+            W, b = W.copy(), b.copy()
+        loss = np.empty(int(iters), dtype=np.float32)
+        ms = ctypes.c_double()
+        self._ck(cfunc(self._ctx, which, _ptr(nodes_a), _ptr(labels_dev), len(nodes_a), C, int(iters), float(lr), float(l2),
+                       _ptr(W), _ptr(b), _ptr(loss), ctypes.byref(ms)))
+        return dict(W=W, b=b, loss=loss, ms=ms.value)
+
     def classifier_lossgrad(self, nodes, labels, W, b, which=0, l2=0.0):
         """Loss and gradients of multinomial logistic regression on the rows ``nodes`` of table ``which`` (0 = gen, 1 = dis)
         at (W [C, n_emb], b [C]) (gg_classifier_lossgrad: one fused sweep on the device).  Returns dict(loss, gW, gb)."""
         W, b = self._nc_params("classifier_lossgrad", W, b)
-        C = int(W.shape[0])
-        nodes_a, labels_a = self._nc_args("classifier_lossgrad", nodes, which, C, labels)
-        loss = np.zeros(1, dtype=np.float32)
-        gW = np.empty_like(W)
-        gb = np.empty_like(b)
-        self._ck(lib.gg_classifier_lossgrad(self._ctx, which, _ptr(nodes_a), _ptr(labels_a), len(nodes_a), C, _ptr(W), _ptr(b), float(l2),
-                                            _ptr(loss), _ptr(gW), _ptr(gb)))
-        return dict(loss=float(loss[0]), gW=gW, gb=gb)
+        nodes_a, labels_a = self._nc_args("classifier_lossgrad", nodes, which, int(W.shape[0]), labels)
+        return self._nc_lossgrad(lib.gg_classifier_lossgrad, nodes_a, labels_a, which, l2, W, b)
 
     def classifier_fit(self, nodes, labels, n_class, which=0, iters=200, lr=0.05, l2=1e-4, W=None, b=None):
         """``iters`` steps of full-batch Adam on the logistic-regression loss of the rows ``nodes`` of table ``which``
         (gg_classifier_fit), from zeros unless (W, b) are given; fit on the device, one synchronisation.  Returns
         dict(W fp32 [n_class, n_emb], b fp32 [n_class], loss fp32 [iters] -- the loss before each update --, ms)."""
         nodes_a, labels_a = self._nc_args("classifier_fit", nodes, which, n_class, labels)
-        C = int(n_class)
-        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
-            raise ValueError("classifier_fit: iters must be an integer >= 1, got %r" % (iters,))
-        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
-            raise ValueError("classifier_fit: lr must be > 0 and l2 >= 0, got %r and %r" % (lr, l2))
-        if (W is None) != (b is None):
-            raise ValueError("classifier_fit: give both W and b, or neither")
-        if W is None:
-            W, b = np.zeros((C, self.n_emb), dtype=np.float32), np.zeros(C, dtype=np.float32)
-        else:
-            W, b = self._nc_params("classifier_fit", W, b)
-            if W.shape[0] != C:
-                raise ValueError("classifier_fit: W has %d rows, n_class is %d" % (W.shape[0], C))
-            W, b = W.copy(), b.copy()
-        loss = np.empty(int(iters), dtype=np.float32)
-        ms = ctypes.c_double()
-        self._ck(lib.gg_classifier_fit(self._ctx, which, _ptr(nodes_a), _ptr(labels_a), len(nodes_a), C, int(iters), float(lr), float(l2),
-                                       _ptr(W), _ptr(b), _ptr(loss), ctypes.byref(ms)))
-        return dict(W=W, b=b, loss=loss, ms=ms.value)
+        return self._nc_fit("classifier_fit", lib.gg_classifier_fit, nodes_a, labels_a, n_class, which, iters, lr, l2, W, b)
 
     def classifier_predict(self, nodes, W, b, which=0, logits=False):
         """argmax_c (W . E[node] + b)[c] of the rows ``nodes`` of table ``which``, ties to the lowest class
@@ -680,38 +687,15 @@ class Engine:
         C = int(W.shape[0])
         nodes_a, _ = self._nc_args("classifier_ml_lossgrad", nodes, which, C)
         bits = self._nc_label_bits("classifier_ml_lossgrad", labels, len(nodes_a), C)
-        loss = np.zeros(1, dtype=np.float32)
-        gW = np.empty_like(W)
-        gb = np.empty_like(b)
-        self._ck(lib.gg_classifier_ml_lossgrad(self._ctx, which, _ptr(nodes_a), _ptr(bits), len(nodes_a), C, _ptr(W), _ptr(b), float(l2),
-                                               _ptr(loss), _ptr(gW), _ptr(gb)))
-        return dict(loss=float(loss[0]), gW=gW, gb=gb)
+        return self._nc_lossgrad(lib.gg_classifier_ml_lossgrad, nodes_a, bits, which, l2, W, b)
 
     def classifier_ml_fit(self, nodes, labels, n_class, which=0, iters=200, lr=0.05, l2=1e-4, W=None, b=None):
         """``iters`` steps of full-batch Adam on the one-vs-rest loss of the rows ``nodes`` of table ``which``
         (gg_classifier_ml_fit), from zeros unless (W, b) are given; labels as in ``classifier_ml_lossgrad``.  Returns
         dict(W fp32 [n_class, n_emb], b fp32 [n_class], loss fp32 [iters] -- the loss before each update --, ms)."""
         nodes_a, _ = self._nc_args("classifier_ml_fit", nodes, which, n_class)
-        C = int(n_class)
-        bits = self._nc_label_bits("classifier_ml_fit", labels, len(nodes_a), C)
-        if isinstance(iters, bool) or int(iters) != iters or int(iters) < 1:
-            raise ValueError("classifier_ml_fit: iters must be an integer >= 1, got %r" % (iters,))
-        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
-            raise ValueError("classifier_ml_fit: lr must be > 0 and l2 >= 0, got %r and %r" % (lr, l2))
-        if (W is None) != (b is None):
-            raise ValueError("classifier_ml_fit: give both W and b, or neither")
-        if W is None:
-            W, b = np.zeros((C, self.n_emb), dtype=np.float32), np.zeros(C, dtype=np.float32)
-        else:
-            W, b = self._nc_params("classifier_ml_fit", W, b)
-            if W.shape[0] != C:
-                raise ValueError("classifier_ml_fit: W has %d rows, n_class is %d" % (W.shape[0], C))
-            W, b = W.copy(), b.copy()
-        loss = np.empty(int(iters), dtype=np.float32)
-        ms = ctypes.c_double()
-        self._ck(lib.gg_classifier_ml_fit(self._ctx, which, _ptr(nodes_a), _ptr(bits), len(nodes_a), C, int(iters), float(lr), float(l2),
-                                          _ptr(W), _ptr(b), _ptr(loss), ctypes.byref(ms)))
-        return dict(W=W, b=b, loss=loss, ms=ms.value)
+        bits = self._nc_label_bits("classifier_ml_fit", labels, len(nodes_a), n_class)
+        return self._nc_fit("classifier_ml_fit", lib.gg_classifier_ml_fit, nodes_a, bits, n_class, which, iters, lr, l2, W, b)
 
     def classifier_ml_predict(self, nodes, W, b, which=0, k=None, logits=False):
         """The label sets of the rows ``nodes`` of table ``which`` under (W, b) (gg_classifier_ml_predict).  With ``k`` (one

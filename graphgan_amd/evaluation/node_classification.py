@@ -78,21 +78,33 @@ def host_lossgrad(X, y, W, b, l2):
     return loss, p.T @ X / len(y) + l2 * W, p.sum(axis=0) / len(y)
 
 
-def host_fit(X, y, n_class, iters, lr, l2):
-    """The device's fit on the host in float64: full-batch Adam (0.9, 0.999, 1e-8, bias-corrected) from zeros -> (W, b, loss)."""
-    X = np.asarray(X, dtype=np.float64)
-    theta = np.zeros(n_class * X.shape[1] + n_class)
+def _adam(lossgrad, theta0, shape, iters, lr):
+    """``iters`` steps of full-batch Adam (0.9, 0.999, 1e-8, bias-corrected, step count from 1) on theta = (W.ravel(), b) of
+    ``shape`` = (n_class, d) from ``theta0``; ``lossgrad(W, b)`` -> (loss, gW, gb) -> (W, b, loss [iters], before each update)."""
+    n_class, d = shape
+    cd = n_class * d
+    theta = theta0
     m, v = np.zeros_like(theta), np.zeros_like(theta)
-    cd = n_class * X.shape[1]
     losses = np.zeros(iters)
     for t in range(1, iters + 1):
-        loss, gW, gb = host_lossgrad(X, y, theta[:cd].reshape(n_class, -1), theta[cd:], l2)
+        loss, gW, gb = lossgrad(theta[:cd].reshape(n_class, -1), theta[cd:])
         losses[t - 1] = loss
         g = np.concatenate([gW.ravel(), gb])
         m = 0.9 * m + (1 - 0.9) * g
         v = 0.999 * v + (1 - 0.999) * g * g
         theta = theta - lr * (m / (1 - 0.9 ** t)) / (np.sqrt(v / (1 - 0.999 ** t)) + 1e-8)
     return theta[:cd].reshape(n_class, -1).copy(), theta[cd:].copy(), losses
+
+
+def _host_fit(lossgrad, X, labels, n_class, iters, lr, l2):
+    """``_adam`` from zeros on ``lossgrad`` (host_lossgrad or host_ml_lossgrad) of the float64 rows X and their labels"""
+    X = np.asarray(X, dtype=np.float64)
+    return _adam(lambda W, b: lossgrad(X, labels, W, b, l2), np.zeros(n_class * X.shape[1] + n_class), (n_class, X.shape[1]), iters, lr)
+
+
+def host_fit(X, y, n_class, iters, lr, l2):
+    """The device's fit on the host in float64: full-batch Adam (0.9, 0.999, 1e-8, bias-corrected) from zeros -> (W, b, loss)."""
+    return _host_fit(host_lossgrad, X, y, n_class, iters, lr, l2)
 
 
 def host_predict(X, W, b):
@@ -127,20 +139,7 @@ def host_ml_lossgrad(X, Y, W, b, l2):
 
 def host_ml_fit(X, Y, iters, lr, l2):
     """The device's multi-label fit on the host in float64: the Adam of ``host_fit`` from zeros -> (W, b, loss)."""
-    X = np.asarray(X, dtype=np.float64)
-    n_class = np.asarray(Y).shape[1]
-    theta = np.zeros(n_class * X.shape[1] + n_class)
-    m, v = np.zeros_like(theta), np.zeros_like(theta)
-    cd = n_class * X.shape[1]
-    losses = np.zeros(iters)
-    for t in range(1, iters + 1):
-        loss, gW, gb = host_ml_lossgrad(X, Y, theta[:cd].reshape(n_class, -1), theta[cd:], l2)
-        losses[t - 1] = loss
-        g = np.concatenate([gW.ravel(), gb])
-        m = 0.9 * m + (1 - 0.9) * g
-        v = 0.999 * v + (1 - 0.999) * g * g
-        theta = theta - lr * (m / (1 - 0.9 ** t)) / (np.sqrt(v / (1 - 0.999 ** t)) + 1e-8)
-    return theta[:cd].reshape(n_class, -1).copy(), theta[cd:].copy(), losses
+    return _host_fit(host_ml_lossgrad, X, Y, np.asarray(Y).shape[1], iters, lr, l2)
 
 
 def host_ml_predict(X, W, b, k=None):
@@ -191,22 +190,17 @@ class NodeClassifyEval(object):
         tr_n, tr_y, te_n, te_y, n_class = self.split()
         if n_class < 2:
             raise ValueError("node classification: %s holds one label value only" % self.labels_filename)
-        if self.multilabel:
-            k = te_y.sum(axis=1).astype(np.int32) if self.ml_protocol == "topk" else None
-            if self.engine is not None:
-                fit = self.engine.classifier_ml_fit(tr_n, tr_y, n_class, which=self.which, iters=self.iters, lr=self.lr, l2=self.l2)
-                pred = self.engine.classifier_ml_predict(te_n, fit["W"], fit["b"], which=self.which, k=k)
-            else:
-                emd = np.asarray(self.emd, dtype=np.float64)
-                W, b, _ = host_ml_fit(emd[tr_n], tr_y, self.iters, self.lr, self.l2)
-                pred = host_ml_predict(emd[te_n], W, b, k)
-            return dict(ml_metrics(te_y, pred), n_train=int(len(tr_n)), n_test=int(len(te_n)))
-        if self.engine is not None:
-            fit = self.engine.classifier_fit(tr_n, tr_y, n_class, which=self.which, iters=self.iters, lr=self.lr, l2=self.l2)
-            pred = self.engine.classifier_predict(te_n, fit["W"], fit["b"], which=self.which)
+        ml, eng = self.multilabel, self.engine
+        # what the multi-label prediction takes beyond (W, b): with "topk" the test nodes' label counts
+        extra = dict(k=te_y.sum(axis=1).astype(np.int32) if self.ml_protocol == "topk" else None) if ml else {}
+        if eng is not None:
+            fit, predict = (eng.classifier_ml_fit, eng.classifier_ml_predict) if ml else (eng.classifier_fit, eng.classifier_predict)
+            res = fit(tr_n, tr_y, n_class, which=self.which, iters=self.iters, lr=self.lr, l2=self.l2)
+            pred = predict(te_n, res["W"], res["b"], which=self.which, **extra)
         else:
+            lossgrad, predict = (host_ml_lossgrad, host_ml_predict) if ml else (host_lossgrad, host_predict)
             emd = np.asarray(self.emd, dtype=np.float64)
-            W, b, _ = host_fit(emd[tr_n], tr_y, n_class, self.iters, self.lr, self.l2)
-            pred = host_predict(emd[te_n], W, b)
-        acc, f1 = metrics(te_y, pred, n_class)
-        return dict(acc=acc, macro_f1=f1, n_train=int(len(tr_n)), n_test=int(len(te_n)))
+            W, b, _ = _host_fit(lossgrad, emd[tr_n], tr_y, n_class, self.iters, self.lr, self.l2)
+            pred = predict(emd[te_n], W, b, **extra)
+        scores = ml_metrics(te_y, pred) if ml else dict(zip(("acc", "macro_f1"), metrics(te_y, pred, n_class)))
+        return dict(scores, n_train=int(len(tr_n)), n_test=int(len(te_n)))

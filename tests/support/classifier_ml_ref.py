@@ -1,10 +1,11 @@
 """numpy restatement of the multi-label node-classification path (include/graphgan_hip.h, gg_classifier_ml_*) in a chosen dtype:
-one-vs-rest logistic regression -- loss and gradient in the stable forms, the full-batch Adam fit, logits, the two prediction
-rules, the metrics -- and planted multi-label test data.  As in classifier_ref, the float64 run is the reference of the device
-tests and the float32 run of the SAME inputs gives the rounding scale a tolerance is derived from (``classifier_ref.tol``)."""
+one-vs-rest logistic regression -- loss and gradient in the stable forms, the two prediction rules, the metrics -- and planted
+multi-label test data; the Adam fit, the logits and the scatter into a table are classifier_ref's.  As there, the float64 run is
+the reference of the device tests and the float32 run of the SAME inputs gives the rounding scale a tolerance is derived from
+(``classifier_ref.tol``)."""
 import numpy as np
 
-from tests.support.classifier_ref import tol  # noqa: F401  (max(8 dev, 1e-6): the project's rule for this sweep)
+from tests.support.classifier_ref import adam_fit, logits, scatter_into_table, tol  # noqa: F401  (logits, tol: for this module's users)
 
 
 def lossgrad(X, Y, W, b, l2, dtype=np.float64):
@@ -23,29 +24,9 @@ def lossgrad(X, Y, W, b, l2, dtype=np.float64):
     return dtype(loss), gW.astype(dtype), gb.astype(dtype)
 
 
-def fit(X, Y, iters, lr, l2, dtype=np.float64):
-    """Full-batch Adam (0.9, 0.999, 1e-8, bias-corrected, step count from 1) from zeros -> (W, b, loss [iters]); loss[t] is the
-    loss at the parameters before update t."""
-    X = np.asarray(X, dtype=dtype)
-    d, n_class = X.shape[1], np.asarray(Y).shape[1]
-    theta = np.zeros(n_class * d + n_class, dtype=dtype)
-    m, v = np.zeros_like(theta), np.zeros_like(theta)
-    b1, b2, eps, lr = dtype(0.9), dtype(0.999), dtype(1e-8), dtype(lr)
-    cd = n_class * d
-    losses = np.zeros(iters, dtype=dtype)
-    for t in range(1, iters + 1):
-        loss, gW, gb = lossgrad(X, Y, theta[:cd].reshape(n_class, d), theta[cd:], l2, dtype)
-        losses[t - 1] = loss
-        g = np.concatenate([gW.ravel(), gb]).astype(dtype)
-        m = b1 * m + (dtype(1) - b1) * g
-        v = b2 * v + (dtype(1) - b2) * (g * g)
-        c1, c2 = dtype(1.0 - 0.9 ** t), dtype(1.0 - 0.999 ** t)
-        theta = (theta - lr * (m / c1) / (np.sqrt(v / c2) + eps)).astype(dtype)
-    return theta[:cd].reshape(n_class, d).copy(), theta[cd:].copy(), losses
-
-
-def logits(X, W, b, dtype=np.float64):
-    return np.asarray(X, dtype=dtype) @ np.asarray(W, dtype=dtype).T + np.asarray(b, dtype=dtype)
+def fit(X, Y, iters, lr, l2, dtype=np.float64, W=None, b=None):
+    """``adam_fit`` of the one-vs-rest loss; the class count is Y's"""
+    return adam_fit(lossgrad, X, Y, np.asarray(Y).shape[1], iters, lr, l2, dtype, W, b)
 
 
 def predict_topk(z, k):
@@ -97,15 +78,11 @@ def planted(M, d, C, N, seed):
     """Class centres 0.3 randn(C, d); each row draws 1-3 distinct labels and is the sum of their centres + 0.15 randn; the rows
     are scattered into a table of N > M rows at random node ids, the other rows noise
     -> (table fp32 [N, d], nodes int64 [M], Y bool [M, C])."""
-    assert N > M
     rs = np.random.RandomState(seed)
     centre = 0.3 * rs.randn(C, d)
     Y = np.zeros((M, C), dtype=bool)
     n_lab = rs.randint(1, min(3, C) + 1, size=M)
     for i in range(M):
         Y[i, rs.permutation(C)[:n_lab[i]]] = True
-    rows = Y.astype(np.float64) @ centre + 0.15 * rs.randn(M, d)
-    table = 0.3 * rs.randn(N, d)
-    nodes = rs.permutation(N)[:M]
-    table[nodes] = rows
-    return table.astype(np.float32), nodes.astype(np.int64), Y
+    table, nodes = scatter_into_table(Y.astype(np.float64) @ centre + 0.15 * rs.randn(M, d), N, rs)
+    return table, nodes, Y

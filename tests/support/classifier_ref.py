@@ -24,9 +24,9 @@ def lossgrad(X, y, W, b, l2, dtype=np.float64):
     return dtype(loss), gW.astype(dtype), gb.astype(dtype)
 
 
-def fit(X, y, n_class, iters, lr, l2, dtype=np.float64, W=None, b=None):
-    """Full-batch Adam (0.9, 0.999, 1e-8, bias-corrected, step count from 1) from zeros (or W, b) -> (W, b, loss [iters]);
-    loss[t] is the loss at the parameters before update t."""
+def adam_fit(lossgrad, X, labels, n_class, iters, lr, l2, dtype, W=None, b=None):
+    """Full-batch Adam (0.9, 0.999, 1e-8, bias-corrected, step count from 1) on ``lossgrad(X, labels, W, b, l2, dtype)`` from zeros
+    (or W, b), every operation in ``dtype`` -> (W, b, loss [iters]); loss[t] is the loss at the parameters before update t."""
     X = np.asarray(X, dtype=dtype)
     d = X.shape[1]
     W = np.zeros((n_class, d), dtype=dtype) if W is None else np.asarray(W, dtype=dtype).copy()
@@ -37,7 +37,7 @@ def fit(X, y, n_class, iters, lr, l2, dtype=np.float64, W=None, b=None):
     cd = n_class * d
     losses = np.zeros(iters, dtype=dtype)
     for t in range(1, iters + 1):
-        loss, gW, gb = lossgrad(X, y, theta[:cd].reshape(n_class, d), theta[cd:], l2, dtype)
+        loss, gW, gb = lossgrad(X, labels, theta[:cd].reshape(n_class, d), theta[cd:], l2, dtype)
         losses[t - 1] = loss
         g = np.concatenate([gW.ravel(), gb]).astype(dtype)
         m = b1 * m + (dtype(1) - b1) * g
@@ -45,6 +45,11 @@ def fit(X, y, n_class, iters, lr, l2, dtype=np.float64, W=None, b=None):
         c1, c2 = dtype(1.0 - 0.9 ** t), dtype(1.0 - 0.999 ** t)
         theta = (theta - lr * (m / c1) / (np.sqrt(v / c2) + eps)).astype(dtype)
     return theta[:cd].reshape(n_class, d).copy(), theta[cd:].copy(), losses
+
+
+def fit(X, y, n_class, iters, lr, l2, dtype=np.float64, W=None, b=None):
+    """``adam_fit`` of the softmax loss"""
+    return adam_fit(lossgrad, X, y, n_class, iters, lr, l2, dtype, W, b)
 
 
 def logits(X, W, b, dtype=np.float64):
@@ -74,18 +79,25 @@ def metrics(truth, pred):
     return float(np.mean(truth == pred)), float(np.mean(f1))
 
 
-def planted(M, d, C, N, seed):
-    """Class centres 0.3 randn(C, d), rows centre[y] + 0.15 randn, scattered into a table of N > M rows at random node ids,
-    the other rows noise -> (table fp32 [N, d], nodes int64 [M], y int64 [M])."""
+def scatter_into_table(rows, N, rs):
+    """``rows`` [M, d] at random node ids of a table of N > M rows, the other rows noise 0.3 randn (drawn from ``rs``)
+    -> (table fp32 [N, d], nodes int64 [M])"""
+    M, d = rows.shape
     assert N > M
-    rs = np.random.RandomState(seed)
-    centre = 0.3 * rs.randn(C, d)
-    y = rs.randint(0, C, size=M)
-    rows = centre[y] + 0.15 * rs.randn(M, d)
     table = 0.3 * rs.randn(N, d)
     nodes = rs.permutation(N)[:M]
     table[nodes] = rows
-    return table.astype(np.float32), nodes.astype(np.int64), y.astype(np.int64)
+    return table.astype(np.float32), nodes.astype(np.int64)
+
+
+def planted(M, d, C, N, seed):
+    """Class centres 0.3 randn(C, d), rows centre[y] + 0.15 randn, scattered into a table of N > M rows at random node ids,
+    the other rows noise -> (table fp32 [N, d], nodes int64 [M], y int64 [M])."""
+    rs = np.random.RandomState(seed)
+    centre = 0.3 * rs.randn(C, d)
+    y = rs.randint(0, C, size=M)
+    table, nodes = scatter_into_table(centre[y] + 0.15 * rs.randn(M, d), N, rs)
+    return table, nodes, y.astype(np.int64)
 
 
 def tol(ref32, ref64):

@@ -7,11 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from tests.support import classifier_harness as harness
 from tests.support import classifier_ref as ref
+from tests.support.classifier_harness import N_TABLE, compare, tables
 
 pytestmark = pytest.mark.gpu
 
-N_TABLE = 5000
 # (M, d, C): row counts around the 64-row tile, d around the 32-column tiles (8 -> 1, 50 -> 2, 128 -> 4, 256 -> 8), C around the
 # 32-class tiles; (997, 256, 128) is the one shape HERE whose W is staged in k-chunks (the other chunked instances, C > 64 at
 # d > 192 and C > 96 at d > 152, are in test_gpu_classifier_shapes.py)
@@ -27,30 +28,10 @@ def ga():
     return graphgan_amd
 
 
-_tables = {}
-
-
-def tables(d):
-    """two different tables [N_TABLE, d] (generator, discriminator), made once per d"""
-    if d not in _tables:
-        rs = np.random.RandomState(100 + d)
-        _tables[d] = ((0.3 * rs.randn(N_TABLE, d)).astype(np.float32), (0.3 * rs.randn(N_TABLE, d) + 0.05).astype(np.float32))
-    return _tables[d]
-
-
-_engines = {}
-
-
 @pytest.fixture(scope="module")
-def engine_of(ga):
-    def get(d):
-        if d not in _engines:
-            _engines[d] = ga.Engine(*tables(d))
-        return _engines[d]
-    yield get
-    for e in _engines.values():
-        e.close()
-    _engines.clear()
+def engine_of():
+    yield harness.engine_of
+    harness.close_engines()
 
 
 @pytest.mark.parametrize("M,d,C", LOSSGRAD_CASES)
@@ -70,11 +51,7 @@ def test_lossgrad_matches_float64(engine_of, M, d, C):
         r64 = ref.lossgrad(X, y, W, b, l2, np.float64)
         r32 = ref.lossgrad(X, y, W, b, l2, np.float32)
         got = eng.classifier_lossgrad(nodes, y, W, b, which=which, l2=l2)
-        for name, g, w64, w32 in zip(("loss", "gW", "gb"), (got["loss"], got["gW"], got["gb"]), r64, r32):
-            t = ref.tol(w32, w64)
-            err = float(np.max(np.abs(np.asarray(g, dtype=np.float64) - w64)))
-            print("lossgrad (%d, %d, %d) which %d %s: err %.3g tol %.3g" % (M, d, C, which, name, err, t))
-            assert err <= t, (name, which, err, t)
+        compare("lossgrad (%d, %d, %d) which %d" % (M, d, C, which), ("loss", "gW", "gb"), (got["loss"], got["gW"], got["gb"]), r64, r32)
     r0 = ref.lossgrad(tables(d)[0][nodes], y, W, b, l2)[1]
     r1 = ref.lossgrad(tables(d)[1][nodes], y, W, b, l2)[1]
     assert np.max(np.abs(r0 - r1)) > 1e-3  # (the two tables give different gradients: `which` is honoured)
@@ -115,11 +92,7 @@ def test_fit_matches_float64(fits, M, d, C):
     got = f["got"]
     assert got["loss"].shape == (100,) and got["ms"] > 0
     assert got["loss"][0] == pytest.approx(np.log(C), abs=1e-5)  # (zeros: the loss before update 1)
-    for name, g, w64, w32 in zip(("W", "b", "loss"), (got["W"], got["b"], got["loss"]), f["r64"], f["r32"]):
-        t = ref.tol(w32, w64)
-        err = float(np.max(np.abs(np.asarray(g, dtype=np.float64) - w64)))
-        print("fit (%d, %d, %d) %s: err %.3g tol %.3g" % (M, d, C, name, err, t))
-        assert err <= t, (name, err, t)
+    compare("fit (%d, %d, %d)" % (M, d, C), ("W", "b", "loss"), (got["W"], got["b"], got["loss"]), f["r64"], f["r32"])
     assert got["loss"][-1] < 0.5 * got["loss"][0]
 
 

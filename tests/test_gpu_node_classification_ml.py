@@ -7,11 +7,12 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.support import classifier_harness as harness
 from tests.support import classifier_ml_ref as ref
+from tests.support.classifier_harness import N_TABLE, compare, tables
 
 pytestmark = pytest.mark.gpu
 
-N_TABLE = 5000
 # (M, d, C): the 64-row tile edge (63, 64, 65), the 32-column tiles (d = 8 -> 1, 50 -> 2, 128 -> 4, 256 -> 8), the mask-word
 # edges (C = 31, 32, 33, 64, 65, 128); (997, 256, 128) is the one shape HERE whose W is staged in k-chunks (the other chunked
 # instances, C > 64 at d > 192 and C > 96 at d > 152, are in test_gpu_classifier_shapes.py)
@@ -25,30 +26,10 @@ def ga():
     return graphgan_amd
 
 
-_tables = {}
-
-
-def tables(d):
-    """two different tables [N_TABLE, d] (generator, discriminator), made once per d"""
-    if d not in _tables:
-        rs = np.random.RandomState(100 + d)
-        _tables[d] = ((0.3 * rs.randn(N_TABLE, d)).astype(np.float32), (0.3 * rs.randn(N_TABLE, d) + 0.05).astype(np.float32))
-    return _tables[d]
-
-
-_engines = {}
-
-
 @pytest.fixture(scope="module")
-def engine_of(ga):
-    def get(d):
-        if d not in _engines:
-            _engines[d] = ga.Engine(*tables(d))
-        return _engines[d]
-    yield get
-    for e in _engines.values():
-        e.close()
-    _engines.clear()
+def engine_of():
+    yield harness.engine_of
+    harness.close_engines()
 
 
 def random_labels(rs, M, C):
@@ -60,14 +41,6 @@ def random_labels(rs, M, C):
         Y[1] = True
         Y[2] = False
     return Y
-
-
-def compare(tag, names, got, r64, r32):
-    for name, g, w64, w32 in zip(names, got, r64, r32):
-        t = ref.tol(w32, w64)
-        err = float(np.max(np.abs(np.asarray(g, dtype=np.float64) - w64)))
-        print("%s %s: err %.3g tol %.3g" % (tag, name, err, t))
-        assert err <= t, (tag, name, err, t)
 
 
 @pytest.mark.parametrize("M,d,C", LOSSGRAD_CASES)
@@ -220,6 +193,53 @@ def test_predict_exact_ties_go_to_the_lower_class(engine_of):
     assert not eng.classifier_ml_predict(np.arange(n), W0, b0).any()
     low = eng.classifier_ml_predict(np.arange(n), W0, b0, k=np.full(n, 66))
     assert low[:, :66].all() and not low[:, 66:].any()
+
+
+def assert_same_front_end(eng, nodes, W, b, which):
+    """both prediction kernels on the same (nodes, W, b): the same logit bits, and top-1 is the argmax -> (pred, logits)"""
+    pred, z = eng.classifier_predict(nodes, W, b, which=which, logits=True)
+    one, z_ml = eng.classifier_ml_predict(nodes, W, b, which=which, k=np.ones(len(nodes), dtype=np.int32), logits=True)
+    assert np.array_equal(z.view(np.uint32), z_ml.view(np.uint32))
+    want = np.zeros(one.shape, dtype=bool)
+    want[np.arange(len(nodes)), pred] = True
+    assert np.array_equal(one, want)
+    return pred, z
+
+
+# d: 50 is ld = 52, a padded tail; C: one lane-class, exactly one register per lane, the second register (lane + 64) in use,
+# both registers full; M (inside): 1, 5 (the workgroup's second pass has one wavefront working), 4100 (the grid is capped at
+# 1024 workgroups x 4 rows: the row-stride loop runs a second time)
+@pytest.mark.parametrize("d", [8, 50, 256])
+@pytest.mark.parametrize("C", [2, 64, 65, 128])
+def test_both_predict_kernels_give_the_same_logit_bits(engine_of, d, C):
+    """the two kernels share one front end (W and the row in LDS, the dot product in ascending k, + b): no tolerance"""
+    eng = engine_of(d)
+    rs = np.random.RandomState(1000 * d + C)
+    W = (0.5 * rs.randn(C, d)).astype(np.float32)
+    b = (0.5 * rs.randn(C)).astype(np.float32)
+    for M in (1, 5, 4100):
+        nodes = rs.randint(0, N_TABLE, size=M)
+        for which in ((0, 1) if (d, C) == (50, 65) else (0,)):
+            pred, z = assert_same_front_end(eng, nodes, W, b, which)
+            assert z.shape == (M, C) and np.all(np.isfinite(z))
+            assert np.array_equal(pred, np.argmax(z, axis=1))  # (on the device's own logits the rule is exact: numpy's first maximum)
+
+
+def test_both_predict_kernels_agree_on_an_exact_tie(engine_of):
+    """two equal rows of W with equal biases: the two maximal logits are the same bits in both kernels and both take the lower"""
+    eng = engine_of(50)
+    rs = np.random.RandomState(9)
+    C, n = 128, 200
+    sign = (5.0 * np.sign(tables(50)[0][:n].mean(axis=0))).astype(np.float32)
+    for lo, hi in ((1, 3), (5, 70), (64, 127)):
+        W = (0.01 * rs.randn(C, 50)).astype(np.float32)
+        b = np.zeros(C, dtype=np.float32)
+        W[lo] = W[hi] = sign
+        b[lo] = b[hi] = 100.0  # the two identical rows come first everywhere
+        pred, z = assert_same_front_end(eng, np.arange(n), W, b, 0)
+        assert np.array_equal(z[:, lo].view(np.uint32), z[:, hi].view(np.uint32))
+        assert np.all(z[:, lo] > np.delete(z, [lo, hi], axis=1).max(axis=1))
+        assert np.all(pred == lo)
 
 
 def _write_labels(path, nodes, Y, values):
