@@ -75,6 +75,16 @@ engine_nc_l2 = 1e-4
 # "threshold" the classes with a positive logit.
 engine_nc_multilabel = False
 engine_nc_ml_protocol = "topk"
+# learned link prediction (evaluation/link_prediction_lr.py): with engine_lp_classifier = True evaluation() appends, after the
+# app's own lines, "gen_lp:acc= macro_f1= auc= n_train= n_test=" and "dis_lp:..." -- logistic regression on an operator of the two
+# endpoint rows, fitted on the device (gg_edge_classifier_fit) on the training edges and as many sampled non-edges.  Needs
+# test_filename and test_neg_filename.  The fit defaults are provisional: they have not been tuned on any dataset.
+engine_lp_classifier = False
+engine_lp_operator = "hadamard"  # "hadamard" | "average" | "l1" | "l2" (the node2vec paper's table)
+engine_lp_iters = 200
+engine_lp_lr = 0.05
+engine_lp_l2 = 1e-4
+engine_lp_max_train = 1 << 20    # training positives at most (a seeded subset beyond that)
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

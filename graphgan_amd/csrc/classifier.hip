@@ -427,6 +427,226 @@ __global__ __launch_bounds__(256) void nc_predict_kernel(const float *E, int ld,
     }
 }
 
+// ---- link prediction (gg_edge_classifier_*): logistic regression on a binary operator of the two endpoint rows of an edge
+//     x_i = op(E[u_i], E[v_i]) elementwise,   z_i = w . x_i + b                     w fp32 [d], b fp32 [1]
+//     loss = (1/M) sum [softplus(z_i) - y_i z_i] + (l2 / 2) |w|^2,   gw = (1/M) sum (sigmoid(z_i) - y_i) x_i + l2 w
+// One logit per row: nothing for a matrix instruction to do, and the two random row gathers are all the work.
+// edge_sweep_kernel is a persistent grid of min(EC_MAX_GRID, ceil(M / 16)) workgroups (a function of M alone); a trip of a
+// workgroup is 16 edges, trips go to workgroups round robin.  EC_LANES = 16 lanes own an edge; lane l owns the float4 pieces
+// l + 16 j (j < NJ = ceil(ld / 64), a template parameter) of both rows, of w and of the gw accumulator, all in registers across
+// the workgroup's trips.  Memory-level parallelism: the rows of the NEXT trip (2 rows x NJ float4 per lane) are in flight
+// while this one computes, and the ids of the trip after that are in flight behind them, so no row address waits for an id.
+// The logit is a 4-step butterfly over the 16 lanes (every lane ends with the same bits).  The loss stage is the multi-label
+// sweep's: e = exp(-|z|), softplus = max(z, 0) + log1p(e), sigmoid = (z >= 0 ? 1 : e) / (1 + e), the loss in float64.  Columns
+// in [d, ld) and edges behind M give exact zeros.  At the end the 16 lane groups fold through LDS in group order and the
+// workgroup writes part[blockIdx][d + 1 + 2] = gw, gb, loss (high, remainder): the stage nc_reduce_kernel reads at C = 1.  No
+// floating-point atomics.  All four operators are symmetric in their operands bit for bit (a - b and b - a differ in sign alone).
+constexpr int EC_LANES = 16;               // lanes per edge
+constexpr int EC_EDGES = 256 / EC_LANES;   // edges of a trip
+constexpr int EC_MAX_GRID = 1024;          // workgroups of an edge sweep, at most
+constexpr int EC_PREDICT_GRID = 1024;      // workgroups of edge_predict_kernel, at most
+
+struct EdgeArgs {
+    const float *E;              // [n_node, ld]
+    const int32_t *u, *v, *y;    // y: 0 | 1 (the sweep's alone)
+    int64_t m;
+    int ld, d;
+    const float *w, *b;          // [d], [1]
+    float *part;                 // sweep: [grid][d + 3]
+    float *logits;               // predict: [m]
+};
+
+// 0 Hadamard, 1 average, 2 L1, 3 L2 (the node2vec paper's table)
+template <int OP>
+__device__ __forceinline__ float ec_op(float a, float b) {
+    if constexpr (OP == 0) {
+        return a * b;
+    } else if constexpr (OP == 1) {
+        return (a + b) * 0.5f;
+    } else if constexpr (OP == 2) {
+        return fabsf(a - b);
+    } else {
+        const float t = a - b;
+        return t * t;
+    }
+}
+
+// the lane's slice of w: pieces l + 16 j, zero behind d
+template <int NJ>
+__device__ __forceinline__ void ec_load_w(float4 (&w)[NJ], const float *wp, int l, int d) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = 4 * (l + EC_LANES * j);
+        w[j].x = col < d ? wp[col] : 0.f;
+        w[j].y = col + 1 < d ? wp[col + 1] : 0.f;
+        w[j].z = col + 2 < d ? wp[col + 2] : 0.f;
+        w[j].w = col + 3 < d ? wp[col + 3] : 0.f;
+    }
+}
+
+// the lane's pieces of both rows of an edge (zeros for an edge behind M and for pieces behind ld)
+template <int NJ>
+__device__ __forceinline__ void ec_fetch(float4 (&ra)[NJ], float4 (&rb)[NJ], const float *E, int iu, int iv, bool ok, int l, int ld) {
+    const float *pa = E + (int64_t)iu * ld, *pb = E + (int64_t)iv * ld;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = 4 * (l + EC_LANES * j);
+        ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        rb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok && col < ld) {
+            ra[j] = *(const float4 *)(pa + col);
+            rb[j] = *(const float4 *)(pb + col);
+        }
+    }
+}
+
+// x = op(ra, rb) (left in ra; columns behind d: 0) and w . x summed over the edge's 16 lanes: every lane returns the same bits
+template <int OP, int NJ>
+__device__ __forceinline__ float ec_features(float4 (&ra)[NJ], const float4 (&rb)[NJ], const float4 (&w)[NJ], int l, int d) {
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = 4 * (l + EC_LANES * j);
+        float4 x;
+        x.x = col < d ? ec_op<OP>(ra[j].x, rb[j].x) : 0.f;
+        x.y = col + 1 < d ? ec_op<OP>(ra[j].y, rb[j].y) : 0.f;
+        x.z = col + 2 < d ? ec_op<OP>(ra[j].z, rb[j].z) : 0.f;
+        x.w = col + 3 < d ? ec_op<OP>(ra[j].w, rb[j].w) : 0.f;
+        ra[j] = x;
+        z += w[j].x * x.x;
+        z += w[j].y * x.y;
+        z += w[j].z * x.z;
+        z += w[j].w * x.w;
+    }
+#pragma unroll
+    for (int o = EC_LANES / 2; o > 0; o >>= 1) z += __shfl_xor(z, o);
+    return z;
+}
+
+template <int OP, int NJ>
+__global__ __launch_bounds__(256) void edge_sweep_kernel(EdgeArgs a) {
+    __shared__ float gs[EC_EDGES][NC_MAX_D];  // the lane groups' gw
+    __shared__ float gbs[EC_EDGES];
+    __shared__ double ls[EC_EDGES];
+    const int tid = threadIdx.x, g = tid / EC_LANES, l = tid % EC_LANES;
+    const int ld = a.ld, d = a.d;
+    const int64_t n_trips = (a.m + EC_EDGES - 1) / EC_EDGES;
+
+    float4 w[NJ], gw[NJ];
+    ec_load_w<NJ>(w, a.w, l, d);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) gw[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float bias = a.b[0];
+    double loss_acc = 0.0;
+    float gb_acc = 0.f;
+
+    int iu = 0, iv = 0, iy = 0;  // the ids and the label of the trip after the next
+    bool ok = false;
+    auto load_ids = [&](int64_t trip) {  // (a trip behind the last one has every edge behind M)
+        const int64_t e = trip * EC_EDGES + g;
+        ok = e < a.m;
+        iu = ok ? a.u[e] : 0;
+        iv = ok ? a.v[e] : 0;
+        iy = ok ? a.y[e] : 0;
+    };
+    float4 na[NJ], nb[NJ];  // the next trip's rows
+    int ny = 0;
+    bool nok = false;
+
+    load_ids(blockIdx.x);
+    ec_fetch<NJ>(na, nb, a.E, iu, iv, ok, l, ld);
+    ny = iy;
+    nok = ok;
+    load_ids((int64_t)blockIdx.x + gridDim.x);
+    for (int64_t trip = blockIdx.x; trip < n_trips; trip += gridDim.x) {
+        float4 ca[NJ], cb[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            ca[j] = na[j];
+            cb[j] = nb[j];
+        }
+        const int cy = ny;
+        const bool cok = nok;
+        ec_fetch<NJ>(na, nb, a.E, iu, iv, ok, l, ld);
+        ny = iy;
+        nok = ok;
+        load_ids(trip + 2 * (int64_t)gridDim.x);
+
+        const float z = ec_features<OP, NJ>(ca, cb, w, l, d) + bias;
+        const float e = expf(-fabsf(z));
+        const float sg = (z >= 0.f ? 1.f : e) / (1.f + e);
+        const float p = cok ? sg - (float)cy : 0.f;
+        if (l == 0) {
+            if (cok) loss_acc += (double)(fmaxf(z, 0.f) + log1pf(e)) - (cy ? (double)z : 0.0);
+            gb_acc += p;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            gw[j].x += p * ca[j].x;
+            gw[j].y += p * ca[j].y;
+            gw[j].z += p * ca[j].z;
+            gw[j].w += p * ca[j].w;
+        }
+    }
+
+    // the workgroup's partial: the 16 lane groups in group order
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = 4 * (l + EC_LANES * j);
+        if (col < ld) *(float4 *)&gs[g][col] = gw[j];
+    }
+    if (l == 0) {
+        gbs[g] = gb_acc;
+        ls[g] = loss_acc;
+    }
+    __syncthreads();
+    float *part = a.part + (int64_t)blockIdx.x * (d + 3);
+    if (tid < d) {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < EC_EDGES; ++q) s += gs[q][tid];
+        part[tid] = s;
+    }
+    if (tid == 0) {
+        float sb = 0.f;
+        double sl = 0.0;
+        for (int q = 0; q < EC_EDGES; ++q) {
+            sb += gbs[q];
+            sl += ls[q];
+        }
+        const float hi = (float)sl;
+        part[d] = sb;
+        part[d + 1] = hi;
+        part[d + 2] = (float)(sl - (double)hi);
+    }
+}
+
+// edge_predict_kernel: logits[i] = w . op(E[u_i], E[v_i]) + b by the sweep's gather, operator and butterfly (the same bits as
+// the sweep's logit); nothing is summed across edges.  Trips of 16 edges go to min(EC_PREDICT_GRID, ceil(M / 16)) workgroups
+// round robin.
+template <int OP, int NJ>
+__global__ __launch_bounds__(256) void edge_predict_kernel(EdgeArgs a) {
+    const int tid = threadIdx.x, g = tid / EC_LANES, l = tid % EC_LANES;
+    const int64_t n_trips = (a.m + EC_EDGES - 1) / EC_EDGES;
+    float4 w[NJ];
+    ec_load_w<NJ>(w, a.w, l, a.d);
+    const float bias = a.b[0];
+    for (int64_t trip = blockIdx.x; trip < n_trips; trip += gridDim.x) {
+        const int64_t e = trip * EC_EDGES + g;
+        const bool ok = e < a.m;
+        float4 ra[NJ], rb[NJ];
+        ec_fetch<NJ>(ra, rb, a.E, ok ? a.u[e] : 0, ok ? a.v[e] : 0, ok, l, a.ld);
+        const float z = ec_features<OP, NJ>(ra, rb, w, l, a.d) + bias;
+        if (ok && l == 0) a.logits[e] = z;
+    }
+}
+
+typedef void (*EdgeFn)(EdgeArgs);
+#define EC_ROW(k, op) {k<op, 1>, k<op, 2>, k<op, 3>, k<op, 4>}
+const EdgeFn ec_sweeps[4][4] = {EC_ROW(edge_sweep_kernel, 0), EC_ROW(edge_sweep_kernel, 1), EC_ROW(edge_sweep_kernel, 2), EC_ROW(edge_sweep_kernel, 3)};
+const EdgeFn ec_predicts[4][4] = {EC_ROW(edge_predict_kernel, 0), EC_ROW(edge_predict_kernel, 1), EC_ROW(edge_predict_kernel, 2),
+                                  EC_ROW(edge_predict_kernel, 3)};
+
 typedef void (*SweepFn)(SweepArgs);
 #define NC_ROW(ct, ml) {nc_sweep_kernel<ct, 1, ml>, nc_sweep_kernel<ct, 2, ml>, nc_sweep_kernel<ct, 3, ml>, nc_sweep_kernel<ct, 4, ml>, \
                         nc_sweep_kernel<ct, 5, ml>, nc_sweep_kernel<ct, 6, ml>, nc_sweep_kernel<ct, 7, ml>, nc_sweep_kernel<ct, 8, ml>}
@@ -656,6 +876,153 @@ int predict_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t 
     return GG_OK;
 }
 
+// ---- gg_edge_classifier_*: the host side
+struct EdgePlan {
+    int grid, NJ;
+};
+
+EdgePlan edge_plan(int64_t m, int ld, int max_grid) {
+    return EdgePlan{(int)std::min<int64_t>(max_grid, (m + EC_EDGES - 1) / EC_EDGES), cdiv(ld, 4 * EC_LANES)};
+}
+
+// device state of an edge fit or loss-and-gradient call; theta = (w [d], b [1])
+struct EdgeFit {
+    ScopedBuf u, v, y, theta, mom, var, grad, part, loss;
+};
+
+int check_edges(gg_ctx *ctx, const char *fn, int which, int op, const int32_t *u, const int32_t *v, int64_t m) {
+    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator), got %d", fn, which);
+    GG_CHECK(ctx, op >= 0 && op <= 3, GG_EINVAL, "%s: op = %d outside [0, 3] (0 Hadamard, 1 average, 2 L1, 3 L2)", fn, op);
+    GG_CHECK(ctx, m >= 1 && m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld outside [1, 2^31 - 1]", fn, (long long)m);
+    GG_CHECK(ctx, ctx->n_emb <= NC_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, NC_MAX_D, ctx->n_emb);
+    GG_CHECK(ctx, u != nullptr, GG_EINVAL, "%s: u is NULL", fn);
+    GG_CHECK(ctx, v != nullptr, GG_EINVAL, "%s: v is NULL", fn);
+    for (int64_t i = 0; i < m; ++i) {
+        GG_CHECK(ctx, u[i] >= 0 && u[i] < ctx->n_node, GG_EINVAL, "%s: node id u = %d (entry %lld) outside [0, %d)", fn, u[i], (long long)i, ctx->n_node);
+        GG_CHECK(ctx, v[i] >= 0 && v[i] < ctx->n_node, GG_EINVAL, "%s: node id v = %d (entry %lld) outside [0, %d)", fn, v[i], (long long)i, ctx->n_node);
+    }
+    return GG_OK;
+}
+
+int check_edge_labels(gg_ctx *ctx, const char *fn, const int32_t *y, int64_t m) {
+    GG_CHECK(ctx, y != nullptr, GG_EINVAL, "%s: y is NULL", fn);
+    for (int64_t i = 0; i < m; ++i) GG_CHECK(ctx, y[i] == 0 || y[i] == 1, GG_EINVAL, "%s: y = %d (entry %lld) is neither 0 nor 1", fn, y[i], (long long)i);
+    return GG_OK;
+}
+
+// the edges, the labels (y may be NULL: prediction) and theta = (w, b) on the device; every allocation comes before the first copy
+hipError_t edge_upload(gg_ctx *ctx, EdgeFit &f, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m, const float *w, const float *b) {
+    const size_t d = ctx->n_emb, ids = sizeof(int32_t) * (size_t)m;
+    hipError_t e = f.u.reserve(ids);
+    if (e == hipSuccess) e = f.v.reserve(ids);
+    if (e == hipSuccess && y) e = f.y.reserve(ids);
+    if (e == hipSuccess) e = f.theta.reserve(sizeof(float) * (d + 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(f.u.p, u, ids, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.v.p, v, ids, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && y) e = hipMemcpyAsync(f.y.p, y, ids, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.p, w, sizeof(float) * d, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.theta.as<float>() + d, b, sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    return e;
+}
+
+// edge sweep + reduce of theta on ctx->stream: grad [d + 2] = gw, gb, loss; the loss also to *loss_dev
+void enqueue_edge_lossgrad(gg_ctx *ctx, const EdgeFit &f, const EdgePlan &p, int which, int op, int64_t m, float l2, float *loss_dev) {
+    const int d = ctx->n_emb;
+    EdgeArgs a{ctx->model[which].E, f.u.as<int32_t>(), f.v.as<int32_t>(), f.y.as<int32_t>(), m, ctx->ld, d, f.theta.as<float>(), f.theta.as<float>() + d,
+               f.part.as<float>(), nullptr};
+    hipLaunchKernelGGL(ec_sweeps[op][p.NJ - 1], dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(nc_reduce_kernel, dim3(cdiv(d + 1, NC_RED_COLS) + 1), dim3(256), 0, ctx->stream, f.part.as<float>(), p.grid, 1, d, m,
+                       f.theta.as<float>(), l2, f.grad.as<float>(), loss_dev);
+}
+
+int edge_lossgrad_call(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m, const float *w, const float *b,
+                       float l2, float *loss_out, float *gw_out, float *gb_out) {
+    const char *fn = "gg_edge_classifier_lossgrad";
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_edges(ctx, fn, which, op, u, v, m)) return rc;
+    if (const int rc = check_edge_labels(ctx, fn, y, m)) return rc;
+    GG_CHECK(ctx, w && b && loss_out && gw_out && gb_out, GG_EINVAL, "%s: w, b, loss_out, gw_out, gb_out must not be NULL", fn);
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t d = ctx->n_emb;
+    const EdgePlan p = edge_plan(m, ctx->ld, EC_MAX_GRID);
+    EdgeFit f;
+    NC_HIP(f.grad.reserve(sizeof(float) * (d + 2)));
+    NC_HIP(f.part.reserve(sizeof(float) * (d + 3) * p.grid));
+    NC_HIP(edge_upload(ctx, f, u, v, y, m, w, b));
+    enqueue_edge_lossgrad(ctx, f, p, which, op, m, l2, nullptr);
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(gw_out, f.grad.p, sizeof(float) * d, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(gb_out, f.grad.as<float>() + d, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(loss_out, f.grad.as<float>() + d + 1, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
+    return GG_OK;
+}
+
+int edge_fit_call(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m, int iters, float lr, float l2,
+                  float *w_inout, float *b_inout, float *loss_out, double *ms_out) {
+    const char *fn = "gg_edge_classifier_fit";
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_edges(ctx, fn, which, op, u, v, m)) return rc;
+    if (const int rc = check_edge_labels(ctx, fn, y, m)) return rc;
+    GG_CHECK(ctx, w_inout && b_inout, GG_EINVAL, "%s: w_inout and b_inout must not be NULL", fn);
+    GG_CHECK(ctx, iters >= 1 && iters <= 1000000, GG_EINVAL, "%s: iters = %d outside [1, 1000000]", fn, iters);
+    GG_CHECK(ctx, lr > 0.f && std::isfinite(lr), GG_EINVAL, "%s: lr must be finite and > 0", fn);
+    GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t d = ctx->n_emb, n_par = d + 1;
+    const EdgePlan p = edge_plan(m, ctx->ld, EC_MAX_GRID);
+    EdgeFit f;
+    NC_HIP(f.grad.reserve(sizeof(float) * (n_par + 1)));
+    NC_HIP(f.part.reserve(sizeof(float) * (n_par + 2) * p.grid));
+    NC_HIP(f.mom.reserve(sizeof(float) * n_par));
+    NC_HIP(f.var.reserve(sizeof(float) * n_par));
+    NC_HIP(f.loss.reserve(sizeof(float) * iters));
+    NC_HIP(edge_upload(ctx, f, u, v, y, m, w_inout, b_inout));
+    NC_HIP(hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream));
+    NC_HIP(hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream));
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    double b1p = 1.0, b2p = 1.0;
+    for (int t = 0; t < iters; ++t) {
+        b1p *= 0.9;
+        b2p *= 0.999;
+        enqueue_edge_lossgrad(ctx, f, p, which, op, m, l2, f.loss.as<float>() + t);
+        hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
+                           f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
+    }
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(w_inout, f.theta.p, sizeof(float) * d, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipMemcpyAsync(b_inout, f.theta.as<float>() + d, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (loss_out) NC_HIP(hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    if (ms_out) *ms_out = ms;
+    return GG_OK;
+}
+
+int edge_predict_call(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, int64_t m, const float *w, const float *b, float *logits_out) {
+    const char *fn = "gg_edge_classifier_predict";
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    if (const int rc = check_edges(ctx, fn, which, op, u, v, m)) return rc;
+    GG_CHECK(ctx, w && b && logits_out, GG_EINVAL, "%s: w, b and logits_out must not be NULL", fn);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    const int d = ctx->n_emb;
+    const EdgePlan p = edge_plan(m, ctx->ld, EC_PREDICT_GRID);
+    EdgeFit f;
+    ScopedBuf d_logits;
+    NC_HIP(d_logits.reserve(sizeof(float) * (size_t)m));
+    NC_HIP(edge_upload(ctx, f, u, v, nullptr, m, w, b));
+    EdgeArgs a{ctx->model[which].E, f.u.as<int32_t>(), f.v.as<int32_t>(), nullptr, m, ctx->ld, d, f.theta.as<float>(), f.theta.as<float>() + d, nullptr,
+               d_logits.as<float>()};
+    hipLaunchKernelGGL(ec_predicts[op][p.NJ - 1], dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    NC_HIP(hipGetLastError());
+    NC_HIP(hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    NC_HIP(hipStreamSynchronize(ctx->stream));
+    return GG_OK;
+}
+
 }  // namespace
 
 }  // namespace gg
@@ -692,4 +1059,20 @@ extern "C" int gg_classifier_predict(gg_ctx *ctx, int which, const int32_t *node
 extern "C" int gg_classifier_ml_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
                                         const int32_t *k, uint32_t *pred_bits, float *logits_out) {
     return predict_call(ctx, "gg_classifier_ml_predict", true, which, nodes, m, n_class, W, b, k, pred_bits, logits_out);
+}
+
+// gg_edge_classifier_lossgrad, gg_edge_classifier_fit, gg_edge_classifier_predict: see include/graphgan_hip.h.
+extern "C" int gg_edge_classifier_lossgrad(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m,
+                                           const float *w, const float *b, float l2, float *loss_out, float *gw_out, float *gb_out) {
+    return edge_lossgrad_call(ctx, which, op, u, v, y, m, w, b, l2, loss_out, gw_out, gb_out);
+}
+
+extern "C" int gg_edge_classifier_fit(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m, int iters,
+                                      float lr, float l2, float *w_inout, float *b_inout, float *loss_out, double *ms_out) {
+    return edge_fit_call(ctx, which, op, u, v, y, m, iters, lr, l2, w_inout, b_inout, loss_out, ms_out);
+}
+
+extern "C" int gg_edge_classifier_predict(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, int64_t m, const float *w,
+                                          const float *b, float *logits_out) {
+    return edge_predict_call(ctx, which, op, u, v, m, w, b, logits_out);
 }

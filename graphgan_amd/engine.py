@@ -23,6 +23,9 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+EDGE_OPERATORS = ("hadamard", "average", "l1", "l2")  # the `op` numbers 0 .. 3 of gg_edge_classifier_* (the node2vec paper's table)
+
+
 def pack_label_bits(Y, n_class):
     """bool / 0-1 matrix [m, C] -> the multi-hot mask of gg_classifier_ml_*: uint32 [m, ceil(C / 32)], bit c & 31 of word c >> 5
     = Y[i, c]."""
@@ -717,6 +720,81 @@ class Engine:
         self._ck(lib.gg_classifier_ml_predict(self._ctx, which, _ptr(nodes_a), len(nodes_a), C, _ptr(W), _ptr(b), _ptr(k_a), _ptr(bits), _ptr(z)))
         pred = unpack_label_bits(bits, C)
         return (pred, z) if logits else pred
+
+    # ------------------------------------------------------------------ learned link prediction (gg_edge_classifier_*)
+    def _ec_args(self, fn, u, v, which, op, y=None):
+        """-> (op number, u int32, v int32, y int32 or None), refused as the ABI refuses them"""
+        if which not in (0, 1):
+            raise ValueError("%s: which must be 0 (generator) or 1 (discriminator), got %r" % (fn, which))
+        if isinstance(op, str):
+            if op not in EDGE_OPERATORS:
+                raise ValueError("%s: operator must be one of %s or a number in [0, 3], got %r" % (fn, ", ".join(EDGE_OPERATORS), op))
+            op = EDGE_OPERATORS.index(op)
+        elif isinstance(op, bool) or not isinstance(op, (int, np.integer)) or not 0 <= int(op) <= 3:
+            raise ValueError("%s: operator must be one of %s or a number in [0, 3], got %r" % (fn, ", ".join(EDGE_OPERATORS), op))
+        u_a, v_a = np.asarray(u), np.asarray(v)
+        if u_a.ndim != 1 or u_a.size == 0 or u_a.shape != v_a.shape or not (np.issubdtype(u_a.dtype, np.integer) and np.issubdtype(v_a.dtype, np.integer)):
+            raise ValueError("%s: u and v must be non-empty 1-d arrays of integers of one length" % fn)
+        if min(int(u_a.min()), int(v_a.min())) < 0 or max(int(u_a.max()), int(v_a.max())) >= self.n_node:
+            raise ValueError("%s: node id outside [0, %d)" % (fn, self.n_node))
+        if y is None:
+            return int(op), _i32(u_a), _i32(v_a), None
+        y_a = np.asarray(y)
+        if y_a.shape != u_a.shape or not (y_a.dtype == np.bool_ or np.issubdtype(y_a.dtype, np.integer)):
+            raise ValueError("%s: y must be 0 / 1, one per edge" % fn)
+        if y_a.dtype != np.bool_ and (int(y_a.min()) < 0 or int(y_a.max()) > 1):
+            raise ValueError("%s: y must be 0 / 1, one per edge" % fn)
+        return int(op), _i32(u_a), _i32(v_a), _i32(y_a.astype(np.int32))
+
+    def _ec_params(self, fn, w, b):
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if w.shape != (self.n_emb,) or b.shape != (1,):
+            raise ValueError("%s: w must be [%d] and b a scalar, got %r and %r" % (fn, self.n_emb, w.shape, b.shape))
+        return w, b
+
+    def edge_classifier_lossgrad(self, u, v, y, w, b, op="hadamard", which=0, l2=0.0):
+        """Loss and gradients of logistic regression on x = op(E[u], E[v]) of the edges (u[i], v[i]) with labels y[i] in {0, 1},
+        rows of table ``which`` (0 = gen, 1 = dis), at (w [n_emb], b scalar) (gg_edge_classifier_lossgrad: one sweep on the
+        device).  ``op``: "hadamard", "average", "l1", "l2" or its number 0 .. 3.  Returns dict(loss, gw, gb)."""
+        w, b = self._ec_params("edge_classifier_lossgrad", w, b)
+        op, u_a, v_a, y_a = self._ec_args("edge_classifier_lossgrad", u, v, which, op, y)
+        loss, gb = np.zeros(1, dtype=np.float32), np.zeros(1, dtype=np.float32)
+        gw = np.empty_like(w)
+        self._ck(lib.gg_edge_classifier_lossgrad(self._ctx, which, op, _ptr(u_a), _ptr(v_a), _ptr(y_a), len(u_a), _ptr(w), _ptr(b), float(l2),
+                                                 _ptr(loss), _ptr(gw), _ptr(gb)))
+        return dict(loss=float(loss[0]), gw=gw, gb=float(gb[0]))
+
+    def edge_classifier_fit(self, u, v, y, op="hadamard", which=0, iters=200, lr=0.05, l2=1e-4, w=None, b=None):
+        """``iters`` steps of full-batch Adam on the loss of ``edge_classifier_lossgrad`` (gg_edge_classifier_fit), from zeros
+        unless (w, b) are given; fit on the device, one synchronisation.  Returns dict(w fp32 [n_emb], b float, loss fp32 [iters]
+        -- the loss before each update --, ms)."""
+        fn = "edge_classifier_fit"
+        op, u_a, v_a, y_a = self._ec_args(fn, u, v, which, op, y)
+        if isinstance(iters, bool) or int(iters) != iters or not 1 <= int(iters) <= 1000000:
+            raise ValueError("%s: iters must be an integer in [1, 10^6], got %r" % (fn, iters))
+        if not (np.isfinite(lr) and lr > 0) or not (np.isfinite(l2) and l2 >= 0):
+            raise ValueError("%s: lr must be > 0 and l2 >= 0, got %r and %r" % (fn, lr, l2))
+        if (w is None) != (b is None):
+            raise ValueError("%s: give both w and b, or neither" % fn)
+        if w is None:
+            w, b = np.zeros(self.n_emb, dtype=np.float32), np.zeros(1, dtype=np.float32)
+        else:
+            w, b = self._ec_params(fn, w, b)
+            w, b = w.copy(), b.copy()
+        loss = np.empty(int(iters), dtype=np.float32)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_edge_classifier_fit(self._ctx, which, op, _ptr(u_a), _ptr(v_a), _ptr(y_a), len(u_a), int(iters), float(lr), float(l2),
+                                            _ptr(w), _ptr(b), _ptr(loss), ctypes.byref(ms)))
+        return dict(w=w, b=float(b[0]), loss=loss, ms=ms.value)
+
+    def edge_classifier_predict(self, u, v, w, b, op="hadamard", which=0):
+        """The logits w . op(E[u], E[v]) + b of the edges (u[i], v[i]) on table ``which`` (gg_edge_classifier_predict): fp32 [len(u)]."""
+        w, b = self._ec_params("edge_classifier_predict", w, b)
+        op, u_a, v_a, _ = self._ec_args("edge_classifier_predict", u, v, which, op)
+        z = np.empty(len(u_a), dtype=np.float32)
+        self._ck(lib.gg_edge_classifier_predict(self._ctx, which, op, _ptr(u_a), _ptr(v_a), len(u_a), _ptr(w), _ptr(b), _ptr(z)))
+        return z
 
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""

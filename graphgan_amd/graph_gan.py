@@ -43,6 +43,7 @@ except ImportError:
 
 from graphgan_amd import _lib, engine as _engine, parallel, utils  # noqa: E402
 from graphgan_amd.evaluation import link_prediction as lp  # noqa: E402
+from graphgan_amd.evaluation import link_prediction_lr as lplr  # noqa: E402
 from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
@@ -60,6 +61,16 @@ def _check_gen_nll(cfg):
         raise ValueError("engine_gen_nll needs test edges: config.test_filename does not exist under app = 'node_classification'")
 
 
+def _check_lp_classifier(cfg):
+    """the learned link-prediction lines need both test files, under any app (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_lp_classifier", False):
+        return
+    for name in ("test_filename", "test_neg_filename"):
+        path = getattr(cfg, name, None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("engine_lp_classifier needs test edges and test negatives: config.%s does not exist (%r)" % (name, path))
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
@@ -67,6 +78,7 @@ class GraphGAN(object):
         print("reading graphs...")
         # native ingest (same adjacency as utils.read_edges, utils.py:12-47); self.graph[i] still lists i's neighbours
         _check_gen_nll(cfg)
+        _check_lp_classifier(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -442,6 +454,7 @@ class GraphGAN(object):
     def evaluation(self):
         cfg = self.config
         _check_gen_nll(cfg)
+        _check_lp_classifier(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -472,6 +485,18 @@ class GraphGAN(object):
                                           l2=float(_cfg(cfg, "engine_nc_l2", 1e-4)), multilabel=multilabel,
                                           ml_protocol=_cfg(cfg, "engine_nc_ml_protocol", "topk"))
                 results.append((nc.format_ml_results if multilabel else nc.format_results)(cfg.modes[i], nce.eval_node_classification()))
+        if _cfg(cfg, "engine_lp_classifier", False):
+            # learned link prediction (gg_edge_classifier_*): logistic regression on an operator of the two endpoint rows, fitted on
+            # training edges and sampled non-edges; one line per mode: "gen_lp:acc=<a> macro_f1=<f> auc=<u> n_train=<n> n_test=<n>"
+            # (without an engine: the float64 host fit on the .emb text, as the other evaluators re-read it)
+            for i in range(2):
+                emd = None if self.engine is not None else utils.read_embeddings(cfg.emb_filenames[i], n_node=self.n_node, n_embed=cfg.n_emb)
+                lre = lplr.LinkPredictLREval(cfg.train_filename, cfg.test_filename, cfg.test_neg_filename, self.n_node, cfg.n_emb,
+                                             emd=emd, engine=self.engine, which=i, operator=_cfg(cfg, "engine_lp_operator", "hadamard"),
+                                             iters=int(_cfg(cfg, "engine_lp_iters", 200)), lr=float(_cfg(cfg, "engine_lp_lr", 0.05)),
+                                             l2=float(_cfg(cfg, "engine_lp_l2", 1e-4)), seed=self.seed,
+                                             max_train=int(_cfg(cfg, "engine_lp_max_train", 1 << 20)))
+                results.append(lplr.format_results(cfg.modes[i], lre.eval_link_prediction()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -474,6 +474,37 @@ int gg_classifier_ml_fit(gg_ctx *ctx, int which, const int32_t *nodes, const uin
 int gg_classifier_ml_predict(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int n_class, const float *W, const float *b,
                              const int32_t *k /* [m] or NULL */, uint32_t *pred_bits /* [m][CW] */, float *logits_out /* NULL or [m, n_class] */);
 
+/* ---- learned link prediction (additive entry points; GG_ABI_VERSION stays 9).  The protocol of the GraphGAN and node2vec
+ * papers: a binary operator on the two endpoint rows of an edge, logistic regression on the result.  The rows are the FROZEN
+ * rows of table `which`, gathered by node id from the resident table; nothing of size m x n_emb crosses to the host.  With
+ * d = n_emb, w fp32 [d], b fp32 [1], edges i = 0 .. m - 1 (u[i], v[i]) with labels y[i] in {0, 1}:
+ *   x_i  = op(E[u[i]], E[v[i]]) elementwise:  op 0 Hadamard a b, 1 average (a + b) 0.5f, 2 L1 |a - b|, 3 L2 (a - b)^2
+ *          (the numbering of the node2vec paper's table; fp32).  All four are symmetric: exchanging u and v changes no output bit.
+ *   z_i  = w . x_i + b
+ *   loss = (1/m) sum_i [softplus(z_i) - y_i z_i] + (l2 / 2) |w|^2                    (the bias is not regularised)
+ *   gw   = (1/m) sum_i (sigmoid(z_i) - y_i) x_i + l2 w,   gb = (1/m) sum_i (sigmoid(z_i) - y_i)
+ * in the stable forms of gg_classifier_ml_*: a logit of +-200 gives a finite loss and a term of exactly 0 - y or 1 - y; the loss
+ * at zero parameters is log 2.
+ * gg_edge_classifier_lossgrad: loss_out[1], gw_out[d], gb_out[1] at the given (w, b): ONE sweep over the edges (both rows of
+ *   an edge are read once, as float4; 16 lanes per edge, the next edges' rows in flight while the current ones compute) and
+ *   the reduction of gg_classifier_*.
+ * gg_edge_classifier_fit: as gg_classifier_fit -- `iters` steps of full-batch Adam (0.9, 0.999, 1e-8, bias-corrected, step count
+ *   from 1) on (w, b) from the values in w_inout / b_inout, which receive the result; loss_out[t] (may be NULL) is the loss
+ *   BEFORE update t; one synchronisation at the end; ms_out (may be NULL): HIP-event time of the iterations.
+ * gg_edge_classifier_predict: logits_out[i] = z_i, the bits the sweep computes for the same edge.
+ * limits       op in [0, 3], n_emb <= 256, 1 <= m <= 2^31 - 1, node ids in [0, n_node), free to repeat, u[i] == v[i] is legal
+ *              (the feature of a self-pair is well defined); y in {0, 1}; iters in [1, 10^6], lr > 0, finite l2 >= 0.  Anything
+ *              else: GG_EINVAL, the gg_last_error text names the entry point and the offending entry, nothing is launched.
+ * determinism  as gg_classifier_*: a grid that depends on m alone, every workgroup folds its lane groups in a fixed order and
+ *              writes one partial to a stage, the stage is added in a fixed order; no floating-point atomics: the same inputs
+ *              and table give the same bits. */
+int gg_edge_classifier_lossgrad(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y /* 0 | 1 */, int64_t m,
+                                const float *w, const float *b /* [1] */, float l2, float *loss_out, float *gw_out /* [d] */, float *gb_out /* [1] */);
+int gg_edge_classifier_fit(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, const int32_t *y, int64_t m, int iters,
+                           float lr, float l2, float *w_inout, float *b_inout, float *loss_out /* [iters] or NULL */, double *ms_out);
+int gg_edge_classifier_predict(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, int64_t m, const float *w,
+                               const float *b, float *logits_out /* [m] */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
