@@ -85,6 +85,13 @@ engine_lp_iters = 200
 engine_lp_lr = 0.05
 engine_lp_l2 = 1e-4
 engine_lp_max_train = 1 << 20    # training positives at most (a seeded subset beyond that)
+# full-ranking link evaluation (evaluation/link_ranking.py): with engine_link_rank = True evaluation() appends, after the *_lp lines
+# and before gen_nll, "gen_rank:MRR= MR= H@1= H@10= H@100= n=" and "dis_rank:..." -- the exact rank of every test edge (both
+# directions) among all nodes but the source and its training neighbours, counted on the device (gg_rank_scores), filtered by the
+# source's other test neighbours.  Needs test_filename; reads no negatives.
+engine_link_rank = False
+engine_link_rank_ks = (1, 10, 100)   # the K of H@K: any positive integers
+engine_link_rank_precision = "fp32"  # ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

@@ -533,6 +533,30 @@ class Engine:
                                     _ptr(col), _ptr(score), ctypes.byref(ms)))
         return dict(col=col, score=score, kernel_ms=ms.value)
 
+    def rank(self, u, v, which=0, precision="fp32", exclude=False):
+        """Full-ranking link evaluation (gg_rank_scores): for each query (u[i], v[i]) the exact rank of column v[i] in row u[i]
+        of E . E^T (no bias) of model ``which`` (0 = gen, 1 = dis) among all candidates, in ``topk``'s order (score
+        descending, column ascending); with ``exclude`` the candidates are every node but u[i] and its neighbours in the
+        resident training graph -- and always the target itself.  precision "fp32" (exact) or "bf16" (bf16 inputs, fp32
+        accumulate).  Nothing of size queries x N is materialised.  Returns dict(rank int32 [m] (1 = best), n_cand int32 [m],
+        score fp32 [m] = s(u, v), kernel_ms)."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("rank: precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        if which not in (0, 1):
+            raise ValueError("rank: which must be 0 (generator) or 1 (discriminator), got %r" % (which,))
+        u_a, v_a = _i32(u).reshape(-1), _i32(v).reshape(-1)
+        if len(u_a) != len(v_a):
+            raise ValueError("rank: u and v must have the same length, got %d and %d" % (len(u_a), len(v_a)))
+        m = len(u_a)
+        rank = np.empty(m, dtype=np.int32)
+        n_cand = np.empty(m, dtype=np.int32)
+        score = np.empty(m, dtype=np.float32)
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_rank_scores(self._ctx, which, _ptr(u_a), _ptr(v_a), m, {"fp32": 0, "bf16": 1}[precision], int(bool(exclude)),
+                                        _ptr(rank), _ptr(n_cand), _ptr(score), ctypes.byref(ms)))
+        return dict(rank=rank, n_cand=n_cand, score=score, kernel_ms=ms.value)
+
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node
         of one walk of ``walk_sample`` on the same slot and mode (graph_gan.py:225-270).  Log-probabilities in fp32, -inf where

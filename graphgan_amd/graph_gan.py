@@ -44,6 +44,7 @@ except ImportError:
 from graphgan_amd import _lib, engine as _engine, parallel, utils  # noqa: E402
 from graphgan_amd.evaluation import link_prediction as lp  # noqa: E402
 from graphgan_amd.evaluation import link_prediction_lr as lplr  # noqa: E402
+from graphgan_amd.evaluation import link_ranking as lrank  # noqa: E402
 from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
@@ -71,6 +72,15 @@ def _check_lp_classifier(cfg):
             raise ValueError("engine_lp_classifier needs test edges and test negatives: config.%s does not exist (%r)" % (name, path))
 
 
+def _check_link_rank(cfg):
+    """the full-ranking lines need the test edges, under any app (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_link_rank", False):
+        return
+    path = getattr(cfg, "test_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_link_rank needs test edges: config.test_filename does not exist (%r)" % (path,))
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
@@ -79,6 +89,7 @@ class GraphGAN(object):
         # native ingest (same adjacency as utils.read_edges, utils.py:12-47); self.graph[i] still lists i's neighbours
         _check_gen_nll(cfg)
         _check_lp_classifier(cfg)
+        _check_link_rank(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -455,6 +466,7 @@ class GraphGAN(object):
         cfg = self.config
         _check_gen_nll(cfg)
         _check_lp_classifier(cfg)
+        _check_link_rank(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -497,6 +509,15 @@ class GraphGAN(object):
                                              l2=float(_cfg(cfg, "engine_lp_l2", 1e-4)), seed=self.seed,
                                              max_train=int(_cfg(cfg, "engine_lp_max_train", 1 << 20)))
                 results.append(lplr.format_results(cfg.modes[i], lre.eval_link_prediction()))
+        if _cfg(cfg, "engine_link_rank", False):
+            # full ranking of the held-out edges (gg_rank_scores, exclude = the training graph; no negatives file): one line per
+            # mode, "gen_rank:MRR=<m> MR=<r> H@1=<h> H@10=<h> H@100=<h> n=<n>" (without an engine: the float64 host ranking on the
+            # .emb text)
+            ks = tuple(_cfg(cfg, "engine_link_rank_ks", lrank.DEFAULT_KS))
+            for i in range(2):
+                lre = lrank.LinkRankEval(cfg.emb_filenames[i], cfg.train_filename, cfg.test_filename, self.n_node, cfg.n_emb,
+                                         engine=self.engine, which=i, ks=ks, precision=_cfg(cfg, "engine_link_rank_precision", "fp32"))
+                results.append(lrank.format_results(cfg.modes[i], lre.eval_link_ranking(), ks))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

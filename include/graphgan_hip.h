@@ -324,6 +324,32 @@ int gg_all_score_reduce(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_
 int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
                    int32_t *out_col, float *out_score, double *kernel_ms_out);
 
+/* gg_rank_scores (additive: a new symbol, the ABI number stays): full-ranking link evaluation.  For each query i the exact
+ * position of the target v[i] among ALL candidate columns of row u[i] of S = E E^T, table E of model `which` (0 = generator,
+ * 1 = discriminator):
+ *   score       s(u, c) = E[u] . E[c], fp32, NO bias -- the bits the tile stream of that precision produces for row u, column c:
+ *               precision 0: v_mfma_f32_32x32x2_f32, the k-ordered fmaf chain from 0.0, bit-identical to gg_all_score with zero
+ *               bias (whose added +0.0 turns a chain that ends at -0.0 into +0.0: the one difference, and a tie); precision 1: a bf16 copy of the table (round to nearest even) on v_mfma_f32_32x32x16_bf16, fp32
+ *               accumulate (n_emb <= 512);
+ *   order       gg_topk_scores' order: score descending, column ascending, -0 counting as +0 (the key ord(score) << 32 | ~col
+ *               of topk_score.hip); "c is ahead of v" below means c comes before v in it;
+ *   candidates  exclude = 0: every node; exclude = 1: every node but u[i] itself and u[i]'s neighbours in the resident training
+ *               graph (gg_set_graph_csr; duplicates in a list are fine; without a graph: GG_EINVAL).  The target v[i] is ALWAYS a
+ *               candidate, also where that rule would drop it: u[i] == v[i] and a target that is a training neighbour are legal;
+ *   results     rank_out[i]   = 1 + the number of candidates c != v[i] ahead of v[i]              (int32 [m]);
+ *               n_cand_out[i] = the number of candidates, the target included once               (int32 [m], or NULL);
+ *               score_out[i]  = s(u[i], v[i])                                                     (fp32 [m], or NULL).
+ *               With `exclude` equal on both sides and an eligible target: rank <= k if and only if gg_topk_scores returns v[i]
+ *               at position rank - 1 of row u[i], with the same score bits.
+ * 1 <= m <= 2^31 - 1; an id outside [0, n_node) is GG_EINVAL (the text names gg_rank_scores and the first bad index; nothing is
+ * launched).  Repeated queries are allowed and give identical outputs; a query's outputs depend on nothing but its own (u, v) --
+ * not on the other queries, their order or the internal passes -- and, the counts being integers, are identical from run to
+ * run.  Non-finite scores: unspecified.  Nothing of size m x n_node exists at any time: the queries are processed in internal
+ * passes of 4 096 with bounded device scratch.  kernel_ms_out (may be NULL): HIP-event time of the tile streams plus the
+ * threshold / correction kernels, summed over the passes (the bf16 copy excluded, as in gg_topk_scores). */
+int gg_rank_scores(gg_ctx *ctx, int32_t which, const int32_t *u, const int32_t *v, int64_t m, int32_t precision, int32_t exclude,
+                   int32_t *rank_out, int32_t *n_cand_out, float *score_out, double *kernel_ms_out);
+
 /* gg_graph_softmax (ABI 9): the generator's distribution G(v | root) of the tree in each given slot, exactly -- the law of the
  * end node of ONE walk of gg_walk_sample on the same slot, mode and tables.  The reference defines it only by how
  * GraphGAN.sample walks (graph_gan.py:225-270; scores all_score = E_g E_g^T + b_g, generator.py:21).  With the reference's
