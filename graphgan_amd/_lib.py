@@ -129,6 +129,8 @@ SIGNATURES = {
     "gg_edge_classifier_fit": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _i64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                _P, _P, _P, _P]),
     "gg_edge_classifier_predict": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _i64, _P, _P, _P]),
+    "gg_kmeans_step": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_kmeans_fit": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

@@ -92,6 +92,15 @@ engine_lp_max_train = 1 << 20    # training positives at most (a seeded subset b
 engine_link_rank = False
 engine_link_rank_ks = (1, 10, 100)   # the K of H@K: any positive integers
 engine_link_rank_precision = "fp32"  # ranking scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
+# node clustering (evaluation/node_clustering.py): with engine_node_clustering = True evaluation() appends, under any app, after the
+# *_rank lines and before gen_nll, "gen_cluster:NMI= ARI= purity= inertia= k= n= iters= empty=" and "dis_cluster:..." -- k-means on
+# the frozen rows of ALL labelled nodes, seeded (k-means++) and fitted on the device (gg_kmeans_step / gg_kmeans_fit), scored against
+# the labels.  Needs labels_filename (lines of "node label"); the restart seeds are engine_seed, engine_seed + 1, ...  The last two
+# defaults are provisional: they have not been tuned on any dataset.
+engine_node_clustering = False
+engine_cluster_k = 0            # clusters; 0 = the number of distinct labels
+engine_cluster_n_init = 4       # k-means++ restarts; the lowest final inertia is kept
+engine_cluster_max_iters = 100  # Lloyd sweeps of a restart at most
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

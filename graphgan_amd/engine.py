@@ -26,6 +26,22 @@ def _i32(a):
 EDGE_OPERATORS = ("hadamard", "average", "l1", "l2")  # the `op` numbers 0 .. 3 of gg_edge_classifier_* (the node2vec paper's table)
 
 
+def kmeans_pp_positions(m, k, seed, dist2_of):
+    """The k-means++ draw of ``Engine.kmeans_seed`` (and of the host evaluator): ``dist2_of(positions so far)`` returns the m
+    squared distances to the nearest chosen centre -> int64 [k] positions.  The rule is stated at ``Engine.kmeans_seed``."""
+    rs = np.random.RandomState([int(seed), 0x4B4D])
+    chosen = [int(rs.randint(m))]
+    while len(chosen) < k:
+        cum = np.cumsum(np.asarray(dist2_of(np.array(chosen, dtype=np.int64)), dtype=np.float64))
+        total = float(cum[-1])
+        if total == 0:
+            chosen.append(int(rs.randint(m)))
+        else:
+            r = rs.random_sample() * total
+            chosen.append(min(int(np.searchsorted(cum, r, side="right")), m - 1))
+    return np.array(chosen, dtype=np.int64)
+
+
 def pack_label_bits(Y, n_class):
     """bool / 0-1 matrix [m, C] -> the multi-hot mask of gg_classifier_ml_*: uint32 [m, ceil(C / 32)], bit c & 31 of word c >> 5
     = Y[i, c]."""
@@ -819,6 +835,101 @@ class Engine:
         z = np.empty(len(u_a), dtype=np.float32)
         self._ck(lib.gg_edge_classifier_predict(self._ctx, which, op, _ptr(u_a), _ptr(v_a), len(u_a), _ptr(w), _ptr(b), _ptr(z)))
         return z
+
+    # ------------------------------------------------------------------ node clustering (gg_kmeans_*)
+    def _km_args(self, fn, nodes, which, k=None):
+        """-> nodes int32, refused as the ABI refuses them"""
+        if which not in (0, 1):
+            raise ValueError("%s: which must be 0 (generator) or 1 (discriminator), got %r" % (fn, which))
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 128):
+            raise ValueError("%s: k must be an integer in [1, 128], got %r" % (fn, k))
+        nodes_a = np.asarray(nodes)
+        if nodes_a.ndim != 1 or nodes_a.size == 0 or not np.issubdtype(nodes_a.dtype, np.integer):
+            raise ValueError("%s: nodes must be a non-empty 1-d array of integers" % fn)
+        if int(nodes_a.min()) < 0 or int(nodes_a.max()) >= self.n_node:
+            raise ValueError("%s: node id outside [0, %d)" % (fn, self.n_node))
+        return _i32(nodes_a)
+
+    def _km_centroids(self, fn, name, values):
+        """a float array [k, n_emb] -> (fp32 copy, None); an integer array of k node ids -> (None, int32)"""
+        a = np.asarray(values)
+        if np.issubdtype(a.dtype, np.integer) and a.dtype != np.bool_:
+            if a.ndim != 1 or not 1 <= a.size <= 128:
+                raise ValueError("%s: %s as node ids must be a 1-d array of 1 .. 128 integers, got shape %r" % (fn, name, a.shape))
+            if int(a.min()) < 0 or int(a.max()) >= self.n_node:
+                raise ValueError("%s: %s holds a node id outside [0, %d)" % (fn, name, self.n_node))
+            return None, _i32(a)
+        if not np.issubdtype(a.dtype, np.floating) or a.ndim != 2 or a.shape[1] != self.n_emb or not 1 <= a.shape[0] <= 128:
+            raise ValueError("%s: %s must be floats [k, %d] with k in [1, 128] or k integer node ids, got %s %r" % (fn, name, self.n_emb, a.dtype, a.shape))
+        return np.array(a, dtype=np.float32, order="C"), None
+
+    def kmeans_step(self, nodes, centroids=None, centroid_nodes=None, which=0, sums=True):
+        """ONE k-means sweep over the rows ``nodes`` of table ``which`` (gg_kmeans_step) at ``centroids`` (floats [k, n_emb]) or at
+        the table rows ``centroid_nodes`` (k node ids; nothing but the ids goes to the device) -- exactly one of the two.
+        Returns dict(assign int32 [m] -- ties to the lowest cluster --, dist2 fp32 [m], inertia float, and unless ``sums`` is
+        False: sums fp32 [k, n_emb], counts int32 [k])."""
+        fn = "kmeans_step"
+        if (centroids is None) == (centroid_nodes is None):
+            raise ValueError("%s: give exactly one of centroids and centroid_nodes" % fn)
+        nodes_a = self._km_args(fn, nodes, which)
+        if centroids is not None:
+            cen, ids = self._km_centroids(fn, "centroids", np.asarray(centroids, dtype=np.float32))
+        else:
+            ids_a = np.asarray(centroid_nodes)
+            if not np.issubdtype(ids_a.dtype, np.integer):
+                raise ValueError("%s: centroid_nodes must be integer node ids" % fn)
+            cen, ids = self._km_centroids(fn, "centroid_nodes", ids_a)
+        k, m = int(len(cen) if cen is not None else len(ids)), len(nodes_a)
+        assign, dist2 = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
+        s = np.empty((k, self.n_emb), dtype=np.float32) if sums else None
+        counts = np.empty(k, dtype=np.int32) if sums else None
+        inertia = np.zeros(1, dtype=np.float64)
+        self._ck(lib.gg_kmeans_step(self._ctx, which, _ptr(nodes_a), m, k, _ptr(cen), _ptr(ids), _ptr(assign), _ptr(dist2), _ptr(s), _ptr(counts),
+                                    _ptr(inertia)))
+        out = dict(assign=assign, dist2=dist2, inertia=float(inertia[0]))
+        if sums:
+            out.update(sums=s, counts=counts)
+        return out
+
+    def kmeans_fit(self, nodes, k=None, init=None, max_iters=100, which=0):
+        """Lloyd's k-means on the rows ``nodes`` of table ``which`` (gg_kmeans_fit), fitted on the device with one
+        synchronisation.  ``init``: floats [k, n_emb], or k node ids (the start is those table rows); ``k`` may be left out (it
+        is ``len(init)``).  Stops at the first sweep (from the second on) that changes no assignment, or after ``max_iters``
+        sweeps without a last update, so the returned state is consistent: ``kmeans_step`` at the returned centroids gives the
+        returned assign, dist2, counts and last inertia bit for bit.  An empty cluster keeps its centroid.  Returns
+        dict(centroids fp32 [k, n_emb], assign int32 [m], dist2 fp32 [m], counts int32 [k], inertia float64 [iters], iters,
+        converged, ms)."""
+        fn = "kmeans_fit"
+        if init is None:
+            raise ValueError("%s: init is required (floats [k, n_emb] or k node ids; Engine.kmeans_seed draws them)" % fn)
+        nodes_a = self._km_args(fn, nodes, which, k)
+        cen, ids = self._km_centroids(fn, "init", init)
+        n_k = int(len(cen) if cen is not None else len(ids))
+        if k is not None and int(k) != n_k:
+            raise ValueError("%s: init has %d centroids, k is %d" % (fn, n_k, int(k)))
+        if isinstance(max_iters, bool) or int(max_iters) != max_iters or not 1 <= int(max_iters) <= 1000000:
+            raise ValueError("%s: max_iters must be an integer in [1, 10^6], got %r" % (fn, max_iters))
+        T, m = int(max_iters), len(nodes_a)
+        if cen is None:
+            cen = np.zeros((n_k, self.n_emb), dtype=np.float32)
+        assign, dist2 = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float32)
+        counts = np.empty(n_k, dtype=np.int32)
+        inertia = np.zeros(T, dtype=np.float64)
+        iters, conv, ms = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        self._ck(lib.gg_kmeans_fit(self._ctx, which, _ptr(nodes_a), m, n_k, T, _ptr(cen), _ptr(ids), _ptr(assign), _ptr(dist2), _ptr(counts),
+                                   _ptr(inertia), ctypes.byref(iters), ctypes.byref(conv), ctypes.byref(ms)))
+        return dict(centroids=cen, assign=assign, dist2=dist2, counts=counts, inertia=inertia[:iters.value].copy(), iters=int(iters.value),
+                    converged=bool(conv.value), ms=ms.value)
+
+    def kmeans_seed(self, nodes, k, seed, which=0):
+        """k-means++ seeding driven from the host over device distances -> int64 [k] POSITIONS into ``nodes``.  The rule:
+        rs = RandomState([seed, 0x4B4D]); the first centre is position rs.randint(m); for every further centre dist2 comes from
+        ``kmeans_step(nodes, centroid_nodes=<the centres so far>)`` (m floats to the host, never m x n_emb), cum = its float64
+        cumulative sum, r = rs.random_sample() * cum[-1], position = min(searchsorted(cum, r, side="right"), m - 1); where
+        cum[-1] == 0 the position is rs.randint(m)."""
+        nodes_a = self._km_args("kmeans_seed", nodes, which, k)
+        step = lambda chosen: self.kmeans_step(nodes_a, centroid_nodes=nodes_a[chosen], which=which, sums=False)["dist2"]  # noqa: E731
+        return kmeans_pp_positions(len(nodes_a), int(k), seed, step)
 
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""

@@ -48,6 +48,7 @@ from graphgan_amd.evaluation import link_ranking as lrank  # noqa: E402
 from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
+from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -81,6 +82,15 @@ def _check_link_rank(cfg):
         raise ValueError("engine_link_rank needs test edges: config.test_filename does not exist (%r)" % (path,))
 
 
+def _check_node_clustering(cfg):
+    """the clustering lines need the labels file, under any app (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_node_clustering", False):
+        return
+    path = getattr(cfg, "labels_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_node_clustering needs labels: config.labels_filename does not exist (%r)" % (path,))
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
@@ -90,6 +100,7 @@ class GraphGAN(object):
         _check_gen_nll(cfg)
         _check_lp_classifier(cfg)
         _check_link_rank(cfg)
+        _check_node_clustering(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -467,6 +478,7 @@ class GraphGAN(object):
         _check_gen_nll(cfg)
         _check_lp_classifier(cfg)
         _check_link_rank(cfg)
+        _check_node_clustering(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -518,6 +530,15 @@ class GraphGAN(object):
                 lre = lrank.LinkRankEval(cfg.emb_filenames[i], cfg.train_filename, cfg.test_filename, self.n_node, cfg.n_emb,
                                          engine=self.engine, which=i, ks=ks, precision=_cfg(cfg, "engine_link_rank_precision", "fp32"))
                 results.append(lrank.format_results(cfg.modes[i], lre.eval_link_ranking(), ks))
+        if _cfg(cfg, "engine_node_clustering", False):
+            # k-means on the frozen rows of all labelled nodes (gg_kmeans_step / gg_kmeans_fit), scored against the labels: one line
+            # per mode, "gen_cluster:NMI=<n> ARI=<a> purity=<p> inertia=<i> k=<k> n=<n> iters=<t> empty=<e>" (without an engine: the
+            # float64 host k-means on the .emb text)
+            for i in range(2):
+                nce = ncl.NodeClusterEval(cfg.emb_filenames[i], cfg.labels_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i,
+                                          k=int(_cfg(cfg, "engine_cluster_k", 0)), n_init=int(_cfg(cfg, "engine_cluster_n_init", 4)),
+                                          max_iters=int(_cfg(cfg, "engine_cluster_max_iters", 100)), seed=self.seed)
+                results.append(ncl.format_results(cfg.modes[i], nce.eval_node_clustering()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -531,6 +531,41 @@ int gg_edge_classifier_fit(gg_ctx *ctx, int which, int op, const int32_t *u, con
 int gg_edge_classifier_predict(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, int64_t m, const float *w,
                                const float *b, float *logits_out /* [m] */);
 
+/* ---- node clustering (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * Lloyd's k-means on the FROZEN rows of table `which` (0 = generator, 1 = discriminator), gathered by node id from the resident
+ * table; nothing of size m x n_emb crosses to the host.  With d = n_emb, centroids fp32 [k, d] row-major, rows i = 0 .. m - 1:
+ *   h_c     = |c_c|^2 / 2 (fp32, columns ascending),   g_ic = h_c - x_i . c_c,   x_i = E[nodes[i]]
+ *   a_i     = argmin_{c < k} g_ic, TIES TO THE LOWEST CLUSTER INDEX; a row whose scores are all NaN gets cluster 0, and no index
+ *             outside [0, k) is ever produced (non-finite tables are otherwise out of contract)
+ *   dist2_i = max(0, |x_i|^2 + 2 g_{i, a_i}),   inertia = sum_i dist2_i (float64)
+ *   sums[c] = sum_{a_i = c} x_i (fp32; the one-hot product only adds),   counts[c] = |{i : a_i = c}| (integers)
+ * gg_kmeans_step: ONE sweep over the rows (every row is read once; both products on v_mfma_f32_32x32x2_f32) plus the reduction,
+ *   at the given centroids.  Exactly one of `centroids` (values) and `centroid_nodes` (centroid c = row centroid_nodes[c] of the
+ *   same table: the bits of both forms are equal) is non-NULL, else GG_EINVAL.  Every output may be NULL; with sums_out and
+ *   counts_out both NULL the sweep skips the second product (the same assign, dist2 and inertia bits).
+ * gg_kmeans_fit: sweep t = 1 .. max_iters assigns against C_t and gives a_t, sums, counts, inertia_t; inertia_out[t - 1] is
+ *   written for the sweeps that ran, later entries are not.  After sweep t:
+ *     1. t >= 2 and a_t == a_{t-1}:  stop, iters = t, converged = 1, C_t unchanged (a fixed point of the update);
+ *     2. else t == max_iters:        stop, iters = t, converged = 0, NO update;
+ *     3. else C_{t+1}[c] = sums[c] / (float)counts[c] (one IEEE fp32 division); an EMPTY cluster keeps its centroid bits.
+ *   The returned centroids, assign, dist2, counts and last inertia are therefore mutually consistent: gg_kmeans_step at the
+ *   returned centroids reproduces them bit for bit -- the fit's sweeps and reductions are the same kernels on the same grid.
+ *   C_1 = centroids_inout, or with init_nodes the table rows init_nodes[c]; centroids_inout receives the result.  All
+ *   max_iters iterations are enqueued behind one another, the stop is a device-side flag, one synchronisation at the end.
+ *   ms_out (may be NULL): HIP-event time of the iterations.  assign_out, dist2_out, counts_out, inertia_out, iters_out,
+ *   converged_out may be NULL.
+ * limits       1 <= k <= 128, n_emb <= 256, 1 <= m <= 2^31 - 1, node ids (nodes, centroid_nodes, init_nodes) in [0, n_node),
+ *              free to repeat; m < k is legal (clusters stay empty); max_iters in [1, 10^6].  Anything else: GG_EINVAL, the
+ *              gg_last_error text names the limit, nothing is launched.
+ * determinism  as gg_classifier_*: a grid that depends on m alone, every workgroup writes its partials to a stage, a second
+ *              kernel adds the stage in a fixed order; no floating-point atomics: the same inputs and table give the same bits. */
+int gg_kmeans_step(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int k, const float *centroids /* [k * d] or NULL */,
+                   const int32_t *centroid_nodes /* [k] or NULL */, int32_t *assign_out /* [m] or NULL */, float *dist2_out /* [m] or NULL */,
+                   float *sums_out /* [k * d] or NULL */, int32_t *counts_out /* [k] or NULL */, double *inertia_out /* [1] or NULL */);
+int gg_kmeans_fit(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int k, int max_iters, float *centroids_inout /* [k * d] */,
+                  const int32_t *init_nodes /* [k] or NULL */, int32_t *assign_out, float *dist2_out, int32_t *counts_out,
+                  double *inertia_out /* [max_iters] or NULL */, int32_t *iters_out, int32_t *converged_out, double *ms_out);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
