@@ -2,29 +2,19 @@
 //     z = W . E[node] + b                         W fp32 [C, d], b fp32 [C]
 //     loss = -(1/M) sum log softmax(z)[label] + (l2 / 2) |W|^2            (the bias is not regularised)
 //     gW = (1/M) sum (p - onehot) E[node]^T + l2 W,   gb = (1/M) sum (p - onehot)
-// nc_sweep_kernel is the hot path: ONE sweep over the M rows gives the loss and both gradients.  A persistent workgroup (256
-// threads, 4 wavefronts) walks 64-row tiles; per tile
-//   1. the rows are gathered into LDS (Xs; the next tile's rows are already in flight to registers while this one computes),
-//   2. logits  Z[64, C] = Xs . W^T on v_mfma_f32_32x32x2_f32, W staged in LDS (Ws) once per workgroup -- in k-chunks per tile
-//      only where C x d does not fit beside the tile: C > 96 at ld > 152 and C > 64 at ld > 192 (sweep_plan; six of the
-//      32 (CT, DT) instances at full tiles: (4, 5 .. 8), (3, 7), (3, 8)),
-//   3. a max-subtracted softmax per row in LDS (4 threads per row), the row's loss term, P = p - onehot left in LDS (Ps),
-//   4. gradient  G[C, d] += P^T . Xs on the same matrix instruction, the accumulators in registers across all tiles of the
-//      workgroup; gb += column sums of Ps.
-// CT = ceil(C / 32) class tiles and DT = ceil(ld / 32) column tiles are template parameters: the accumulators are register
-// arrays with compile-time indices (an instantiation that spills fails the build, check_no_scratch.sh).
-// Determinism: the grid is min(NC_MAX_GRID, ceil(M / 64)) -- a function of M alone --, tiles go to workgroups round robin,
-// every workgroup writes its partial [C d + C + 2] to a stage and nc_reduce_kernel sums the stage in a fixed order.  No
-// floating-point atomics anywhere: two calls with the same inputs give the same bits.  The loss partial is a float64 sum kept
-// as two floats (high part, remainder): one float would round a sum of 64 C-term rows at 2^-24 of ITS size, more than half a
-// float32 spacing of the mean loss at small M.
+// nc_sweep_kernel is the hot path: ONE sweep over the M rows gives the loss and both gradients.  It is the row-tile sweep of
+// row_tiles.h (gather, logits Z = Xs . W^T, row stage, gradient G += P^T . Xs; the geometry, the barriers and the launch plan
+// are described there) with this file's row stage: a max-subtracted softmax per row in LDS (4 threads per row), the row's loss
+// term, P = p - onehot left in LDS; gb += column sums of P.
+// Every workgroup writes its partial [C d + C + 2] (gW, gb, the float64 loss as two floats) to a stage and nc_reduce_kernel sums
+// the stage in a fixed order.  No floating-point atomics anywhere: two calls with the same inputs give the same bits.
 // nc_adam_kernel: full-batch Adam on (W, b); nc_predict_kernel: logits + argmax (ties to the lowest class).
 //
 // Multi-label (gg_classifier_ml_*): one-vs-rest logistic regression against a multi-hot mask uint32 [M][CT] (bit c & 31 of word
 // c >> 5 = row has class c):
 //     loss = (1/M) sum_i sum_c [softplus(z_ic) - y_ic z_ic] + (l2 / 2) |W|^2,   gW = (1/M) sum (sigmoid(z) - y) E[node]^T + l2 W
-// It is the SAME sweep with a second compile-time variant of step 3 (template parameter ML; steps 1, 2, 4, the epilogue, the
-// stage, nc_reduce_kernel and nc_adam_kernel are shared): per class, with e = exp(-|z|), softplus(z) = max(z, 0) + log1p(e) and
+// It is the SAME sweep with a second compile-time variant of the row stage (template parameter ML; everything else, the stage,
+// nc_reduce_kernel and nc_adam_kernel are shared): per class, with e = exp(-|z|), softplus(z) = max(z, 0) + log1p(e) and
 // sigmoid(z) = (z >= 0 ? 1 : e) / (1 + e) -- finite at any logit, and exactly 0 or 1 once e underflows.
 // nc_ml_predict_kernel: logits, the rank of every class in (logit descending, class ascending) and the mask of the first k[i]
 // classes of that order (or of the classes with z > 0).
@@ -33,22 +23,13 @@
 #include <algorithm>
 #include <vector>
 
-#include "gg_internal.h"
+#include "row_tiles.h"
 
 namespace gg {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int NC_RT = 64;           // rows per tile
-constexpr int NC_MAX_GRID = 512;    // workgroups of a sweep, at most
-constexpr int NC_MAX_C = 128, NC_MAX_D = 256;
-constexpr size_t NC_LDS = 150 * 1024;  // dynamic LDS of a sweep workgroup, at most
 constexpr int NC_RED_COLS = 32, NC_RED_SLICES = 8;  // nc_reduce_kernel: columns x stage slices per workgroup
-
-// C/D layout of v_mfma_f32_32x32x2_f32 (score_tiles.h, tile_row)
-__device__ __forceinline__ int nc_tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 struct SweepArgs {
     const float *E;          // [n_node, ld]
@@ -63,105 +44,19 @@ struct SweepArgs {
 
 template <int CT, int DT, bool ML>
 __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
-    constexpr int XS = 32 * DT + 1, PS = 32 * CT + 1;       // row strides of Xs / Ps (odd: conflict-free column walks)
-    constexpr int N1 = (2 * CT + 3) / 4;                     // logit tiles (row half, class tile) per wavefront
-    constexpr int N2 = (CT * DT + 3) / 4;                    // gradient tiles (class tile, column tile) per wavefront
-    constexpr int NPF = 2 * DT;                              // float4 pieces of a tile per thread
+    constexpr int PS = RowTiles<CT, DT>::PS;
     extern __shared__ float nc_lds[];
-    __shared__ float bs[NC_MAX_C];  // the bias
+    __shared__ float bs[RT_MAX_OUT];  // the bias
     __shared__ double red[256];  // the workgroup's loss terms (float64: a sum of M terms of size log C must keep the last digits)
-    float *Xs = nc_lds, *Ps = Xs + NC_RT * XS, *Ws = Ps + NC_RT * PS;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int ld = a.ld, d = a.d, C = a.C, KW = a.KW, WS = KW + 1;
-    const bool w_resident = KW >= ld;
-    const int64_t n_tiles = (a.m + NC_RT - 1) / NC_RT;
-
-    auto stage_w = [&](int k0) {
-        const int kw = min(KW, ld - k0);
-        for (int i = tid; i < 32 * CT * kw; i += 256) {
-            const int c = i / kw, kk = i - c * kw, k = k0 + kk;
-            Ws[c * WS + kk] = (c < C && k < d) ? a.W[(int64_t)c * d + k] : 0.f;
-        }
-    };
-    float4 pf[NPF];
-    auto fetch = [&](int64_t tile) {  // the tile's rows -> registers (rows behind M and columns behind ld: zeros)
-        const int64_t row0 = tile * NC_RT;
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
-            pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (tile < n_tiles && row0 + r < a.m && col < ld) pf[j] = *(const float4 *)(a.E + (int64_t)a.nodes[row0 + r] * ld + col);
-        }
-    };
-
-    f32x16 acc2[N2];
-#pragma unroll
-    for (int i = 0; i < N2; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc2[i][q] = 0.f;
+    const int tid = threadIdx.x, d = a.d, C = a.C;
     double loss_acc = 0.0;
     float gb_acc = 0.f;
 
-    if (tid < C) bs[tid] = a.b[tid];
-    if (w_resident) stage_w(0);
-    fetch(blockIdx.x);
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t row0 = tile * NC_RT;
-        __syncthreads();  // the previous tile's gradient product has read Xs / Ps
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
-            float *x = Xs + r * XS + col;
-            x[0] = pf[j].x; x[1] = pf[j].y; x[2] = pf[j].z; x[3] = pf[j].w;
-        }
-        fetch(tile + gridDim.x);
-        if (w_resident) __syncthreads();
-
-        // 2. logits: unit u = wv + 4 i is (row half u & 1, class tile u >> 1)
-        f32x16 acc1[N1];
-#pragma unroll
-        for (int i = 0; i < N1; ++i)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc1[i][q] = 0.f;
-        for (int k0 = 0; k0 < ld; k0 += KW) {
-            if (!w_resident) {
-                __syncthreads();
-                stage_w(k0);
-                __syncthreads();
-            }
-            const int kmax = min(KW, ld - k0);
-#pragma unroll
-            for (int i = 0; i < N1; ++i) {
-                const int u = wv + 4 * i;
-                if (u < 2 * CT) {
-                    const float *xa = Xs + ((u & 1) * 32 + l31) * XS + k0 + half;
-                    const float *wb = Ws + ((u >> 1) * 32 + l31) * WS + half;
-                    int kk = 0;
-                    for (; kk + 16 <= kmax; kk += 16) {  // (8 steps: their 16 LDS reads are issued ahead of the matrix instructions)
-                        float xv[8], wv8[8];
-#pragma unroll
-                        for (int s = 0; s < 8; ++s) {
-                            xv[s] = xa[kk + 2 * s];
-                            wv8[s] = wb[kk + 2 * s];
-                        }
-#pragma unroll
-                        for (int s = 0; s < 8; ++s) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], wv8[s], acc1[i], 0, 0, 0);
-                    }
-                    for (; kk < kmax; kk += 2) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[kk], wb[kk], acc1[i], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < N1; ++i) {
-            const int u = wv + 4 * i;
-            if (u < 2 * CT) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) Ps[((u & 1) * 32 + nc_tile_row(reg, half)) * PS + (u >> 1) * 32 + l31] = acc1[i][reg];
-            }
-        }
-        __syncthreads();
-
-        // 3. the per-row loss stage of row tid >> 2 by 4 threads (classes q, q + 4, ...); P is zero for rows behind M and padded classes
+    auto setup = [&](const float *, int, bool) {
+        if (tid < C) bs[tid] = a.b[tid];
+    };
+    // the per-row loss stage of row tid >> 2 by 4 threads (classes q, q + 4, ...); P is zero for rows behind M and padded classes
+    auto rows = [&](int64_t row0, const float *, float *Ps) {
         if constexpr (ML) {
             // per-class sigmoid cross-entropy against the row's mask words (word j holds classes 32 j .. 32 j + 31; CT words per
             // row); P = sigmoid(z) - y.  No row maximum, nothing crosses lanes.
@@ -213,51 +108,13 @@ __global__ __launch_bounds__(256) void nc_sweep_kernel(SweepArgs a) {
             }
             for (int c = C + q; c < 32 * CT; c += 4) p[c] = 0.f;
         }
-        __syncthreads();
-
-        // 4. gradient: tile t = wv + 4 i is (class tile t / DT, column tile t % DT); k runs over the 64 rows
-        if (tid < C) {
-#pragma unroll 8
-            for (int r = 0; r < NC_RT; ++r) gb_acc += Ps[r * PS + tid];
-        }
-#pragma unroll
-        for (int i = 0; i < N2; ++i) {
-            const int t = wv + 4 * i;
-            if (t < CT * DT) {
-                const float *pa = Ps + half * PS + (t / DT) * 32 + l31;
-                const float *xb = Xs + half * XS + (t % DT) * 32 + l31;
-#pragma unroll 8
-                for (int k = 0; k < NC_RT; k += 2) acc2[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[k * PS], xb[k * XS], acc2[i], 0, 0, 0);
-            }
-        }
-    }
-
+    };
+    auto column = [&](float p) { gb_acc += p; };  // (a float sum with r ascending)
     // the workgroup's partial: gW [C, d], gb [C], loss (two floats)
     float *part = a.part + (int64_t)blockIdx.x * ((int64_t)C * d + C + 2);
-#pragma unroll
-    for (int i = 0; i < N2; ++i) {
-        const int t = wv + 4 * i;
-        if (t < CT * DT) {
-            const int col = (t % DT) * 32 + l31;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int c = (t / DT) * 32 + nc_tile_row(reg, half);
-                if (c < C && col < d) part[(int64_t)c * d + col] = acc2[i][reg];
-            }
-        }
-    }
+    row_tile_sweep<CT, DT, true>(nc_lds, a.E, a.nodes, a.m, a.ld, d, C, a.W, a.KW, part, setup, rows, column);
     if (tid < C) part[(int64_t)C * d + tid] = gb_acc;
-    red[tid] = loss_acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float hi = (float)red[0];
-        part[(int64_t)C * d + C] = hi;
-        part[(int64_t)C * d + C + 1] = (float)(red[0] - (double)hi);
-    }
+    rt_block_sum(red, loss_acc, part + (int64_t)C * d + C);
 }
 
 // grad[j] = (1/M) sum_g part[g][j] (+ l2 W[j] for j < C d) for the C d + C gradient entries: a workgroup takes NC_RED_COLS
@@ -366,7 +223,7 @@ __global__ __launch_bounds__(256) void nc_ml_predict_kernel(const float *E, int 
                                                            const float *b, const int32_t *k, uint32_t *pred_bits, float *logits) {
     extern __shared__ float nc_lds[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, CW = (C + 31) >> 5;
-    float *Ws = nc_lds, *xs = Ws + C * (ld + 1) + wv * ld, *zs = Ws + C * (ld + 1) + 4 * ld + wv * NC_MAX_C;
+    float *Ws = nc_lds, *xs = Ws + C * (ld + 1) + wv * ld, *zs = Ws + C * (ld + 1) + 4 * ld + wv * RT_MAX_OUT;
     nc_stage_w(Ws, W, C, d, ld);
     for (int64_t row = (int64_t)blockIdx.x * 4 + wv; row < m; row += (int64_t)gridDim.x * 4) {
         nc_stage_row(xs, E + (int64_t)nodes[row] * ld, ld, lane);
@@ -525,7 +382,7 @@ __device__ __forceinline__ float ec_features(float4 (&ra)[NJ], const float4 (&rb
 
 template <int OP, int NJ>
 __global__ __launch_bounds__(256) void edge_sweep_kernel(EdgeArgs a) {
-    __shared__ float gs[EC_EDGES][NC_MAX_D];  // the lane groups' gw
+    __shared__ float gs[EC_EDGES][RT_MAX_D];  // the lane groups' gw
     __shared__ float gbs[EC_EDGES];
     __shared__ double ls[EC_EDGES];
     const int tid = threadIdx.x, g = tid / EC_LANES, l = tid % EC_LANES;
@@ -654,56 +511,31 @@ typedef void (*SweepFn)(SweepArgs);
 const SweepFn nc_sweeps[2][4][8] = {{NC_ROW(1, false), NC_ROW(2, false), NC_ROW(3, false), NC_ROW(4, false)},
                                     {NC_ROW(1, true), NC_ROW(2, true), NC_ROW(3, true), NC_ROW(4, true)}};
 
-// The launch plan of a sweep: template instance, grid (a function of m alone), dynamic LDS and the W k-chunk.
-struct SweepPlan {
+// The launch plan of a sweep (row_tiles.h) with its template instance
+struct SweepPlan : RowTilePlan {
     SweepFn fn;
-    int grid, KW;
-    size_t lds;
 };
 
 SweepPlan sweep_plan(int64_t m, int C, int ld, bool ml) {
-    const int CT = cdiv(C, 32), DT = cdiv(ld, 32);
-    const size_t fixed = sizeof(float) * NC_RT * ((size_t)(32 * DT + 1) + (32 * CT + 1));
-    int KW = (int)((NC_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;
-    KW = KW >= ld ? ld : (KW / 4) * 4;
-    SweepPlan p;
-    p.fn = nc_sweeps[ml ? 1 : 0][CT - 1][DT - 1];
-    p.grid = (int)std::min<int64_t>(NC_MAX_GRID, (m + NC_RT - 1) / NC_RT);
-    p.KW = KW;
-    p.lds = fixed + sizeof(float) * 32 * CT * (size_t)(KW + 1);
-    return p;
+    const RowTilePlan t = row_tile_plan(m, C, ld);
+    return SweepPlan{t, nc_sweeps[ml ? 1 : 0][t.CT - 1][t.DT - 1]};
 }
 
-// A device allocation that lives as long as one call: released when the call returns, on every path -- behind the stream
-// synchronisation, or behind the HIP call that failed.
-struct ScopedBuf : DevBuf {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf &) = delete;
-    ScopedBuf &operator=(const ScopedBuf &) = delete;
-    ~ScopedBuf() { release(); }
+// device state of an Adam fit (adam_fit); theta = (W, b)
+struct AdamBufs {
+    ScopedBuf theta, mom, var, grad, loss;
 };
 
-// A HIP call of the entry point `fn`: its failure ends the call with the entry point's name in the error text.
-#define NC_HIP(call)                                                                           \
-    do {                                                                                       \
-        const hipError_t e__ = (call);                                                         \
-        if (e__ != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e__)); \
-    } while (0)
-
 // device state of a fit or loss-and-gradient call
-struct Fit {
-    ScopedBuf nodes, labels, theta, mom, var, grad, part, loss;
+struct Fit : AdamBufs {
+    ScopedBuf nodes, labels, part;
 };
 
 int check_common(gg_ctx *ctx, const char *fn, int which, const int32_t *nodes, int64_t m, int n_class) {
-    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator), got %d", fn, which);
-    GG_CHECK(ctx, n_class >= 2 && n_class <= NC_MAX_C, GG_EINVAL, "%s: n_class = %d outside [2, %d]", fn, n_class, NC_MAX_C);
-    GG_CHECK(ctx, m >= 1 && m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld outside [1, 2^31 - 1]", fn, (long long)m);
-    GG_CHECK(ctx, ctx->n_emb <= NC_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, NC_MAX_D, ctx->n_emb);
-    GG_CHECK(ctx, nodes != nullptr, GG_EINVAL, "%s: nodes is NULL", fn);
-    for (int64_t i = 0; i < m; ++i)
-        GG_CHECK(ctx, nodes[i] >= 0 && nodes[i] < ctx->n_node, GG_EINVAL, "%s: node id %d (entry %lld) outside [0, %d)", fn, nodes[i], (long long)i, ctx->n_node);
-    return GG_OK;
+    return check_rows(ctx, fn, which, nodes, m, [&] {
+        GG_CHECK(ctx, n_class >= 2 && n_class <= RT_MAX_OUT, GG_EINVAL, "%s: n_class = %d outside [2, %d]", fn, n_class, RT_MAX_OUT);
+        return (int)GG_OK;
+    });
 }
 
 int check_labels(gg_ctx *ctx, const char *fn, const int32_t *labels, int64_t m, int n_class) {
@@ -783,13 +615,48 @@ int lossgrad_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t
     const size_t cd = (size_t)C * ctx->n_emb;
     const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    NC_HIP(fit_upload(ctx, f, p, ml, nodes, labels, m, C, W, b));
+    GG_HIP_FN(fit_upload(ctx, f, p, ml, nodes, labels, m, C, W, b));
     enqueue_lossgrad(ctx, f, p, which, m, C, l2, nullptr);
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(gW_out, f.grad.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(gb_out, f.grad.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipGetLastError());
+    GG_HIP_FN(hipMemcpyAsync(gW_out, f.grad.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(gb_out, f.grad.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(loss_out, f.grad.as<float>() + cd + C, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
+    return GG_OK;
+}
+
+// `iters` steps of full-batch Adam on theta = (W [n_w], b [n_b]), shared by the node and the edge classifier: upload() reserves
+// the caller's buffers and copies its inputs (behind the reservations made here: every allocation of a call comes before its
+// first copy), enqueue(loss_dev) puts one loss-and-gradient of theta on ctx->stream (f.grad; the loss also to *loss_dev).
+// The beta powers are float64 products.  Reads back theta, the loss of every iteration and the device time of the loop.
+template <class Upload, class Enqueue>
+int adam_fit(gg_ctx *ctx, const char *fn, AdamBufs &f, size_t n_w, size_t n_b, int iters, float lr, Upload upload, Enqueue enqueue, float *W_inout,
+             float *b_inout, float *loss_out, double *ms_out) {
+    const size_t n_par = n_w + n_b;
+    GG_HIP_FN(f.mom.reserve(sizeof(float) * n_par));
+    GG_HIP_FN(f.var.reserve(sizeof(float) * n_par));
+    GG_HIP_FN(f.loss.reserve(sizeof(float) * iters));
+    GG_HIP_FN(upload());
+    GG_HIP_FN(hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream));
+    GG_HIP_FN(hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream));
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    double b1p = 1.0, b2p = 1.0;
+    for (int t = 0; t < iters; ++t) {
+        b1p *= 0.9;
+        b2p *= 0.999;
+        enqueue(f.loss.as<float>() + t);
+        hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
+                           f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
+    }
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    GG_HIP_FN(hipGetLastError());
+    GG_HIP_FN(hipMemcpyAsync(W_inout, f.theta.p, sizeof(float) * n_w, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(b_inout, f.theta.as<float>() + n_w, sizeof(float) * n_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (loss_out) GG_HIP_FN(hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    if (ms_out) *ms_out = ms;
     return GG_OK;
 }
 
@@ -805,34 +672,12 @@ int fit_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t *nod
     GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
     GG_HIP(ctx, hipSetDevice(ctx->device));
     const int C = n_class;
-    const size_t cd = (size_t)C * ctx->n_emb, n_par = cd + C;
+    const size_t cd = (size_t)C * ctx->n_emb;
     const SweepPlan p = sweep_plan(m, C, ctx->ld, ml);
     Fit f;
-    NC_HIP(fit_upload(ctx, f, p, ml, nodes, labels, m, C, W_inout, b_inout));
-    NC_HIP(f.mom.reserve(sizeof(float) * n_par));
-    NC_HIP(f.var.reserve(sizeof(float) * n_par));
-    NC_HIP(f.loss.reserve(sizeof(float) * iters));
-    NC_HIP(hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream));
-    NC_HIP(hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream));
-    (void)hipEventRecord(ctx->ev0, ctx->stream);
-    double b1p = 1.0, b2p = 1.0;
-    for (int t = 0; t < iters; ++t) {
-        b1p *= 0.9;
-        b2p *= 0.999;
-        enqueue_lossgrad(ctx, f, p, which, m, C, l2, f.loss.as<float>() + t);
-        hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
-                           f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
-    }
-    (void)hipEventRecord(ctx->ev1, ctx->stream);
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(W_inout, f.theta.p, sizeof(float) * cd, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(b_inout, f.theta.as<float>() + cd, sizeof(float) * C, hipMemcpyDeviceToHost, ctx->stream));
-    if (loss_out) NC_HIP(hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    if (ms_out) *ms_out = ms;
-    return GG_OK;
+    return adam_fit(
+        ctx, fn, f, cd, C, iters, lr, [&] { return fit_upload(ctx, f, p, ml, nodes, labels, m, C, W_inout, b_inout); },
+        [&](float *loss_dev) { enqueue_lossgrad(ctx, f, p, which, m, C, l2, loss_dev); }, W_inout, b_inout, loss_out, ms_out);
 }
 
 // gg_classifier_predict / gg_classifier_ml_predict: `pred_out` is int32 [m] (the argmax), or with `ml` the mask words uint32
@@ -849,17 +694,17 @@ int predict_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t 
     const int C = n_class, d = ctx->n_emb, ld = ctx->ld;
     const size_t cd = (size_t)C * d, pred_bytes = sizeof(int32_t) * (size_t)m * (ml ? cdiv(C, 32) : 1), logit_bytes = sizeof(float) * (size_t)m * C;
     // W [C][ld + 1], a row per wavefront, and the ml form's published logits per wavefront
-    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld + (ml ? 4 * (size_t)NC_MAX_C : 0));
+    const size_t lds = sizeof(float) * ((size_t)C * (ld + 1) + 4 * (size_t)ld + (ml ? 4 * (size_t)RT_MAX_OUT : 0));
     const void *kernel = ml ? (const void *)nc_ml_predict_kernel : (const void *)nc_predict_kernel;
     ScopedBuf d_nodes, d_theta, d_k, d_pred, d_logits;
-    NC_HIP(d_nodes.reserve(sizeof(int32_t) * m));
-    NC_HIP(d_theta.reserve(sizeof(float) * (cd + C)));
-    if (k) NC_HIP(d_k.reserve(sizeof(int32_t) * m));
-    NC_HIP(d_pred.reserve(pred_bytes));
-    if (logits_out) NC_HIP(d_logits.reserve(logit_bytes));
-    NC_HIP(upload_nodes_theta(ctx, d_nodes, d_theta, nodes, m, C, W, b));
-    if (k) NC_HIP(hipMemcpyAsync(d_k.p, k, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream));
-    if (lds > 48 * 1024) NC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GG_HIP_FN(d_nodes.reserve(sizeof(int32_t) * m));
+    GG_HIP_FN(d_theta.reserve(sizeof(float) * (cd + C)));
+    if (k) GG_HIP_FN(d_k.reserve(sizeof(int32_t) * m));
+    GG_HIP_FN(d_pred.reserve(pred_bytes));
+    if (logits_out) GG_HIP_FN(d_logits.reserve(logit_bytes));
+    GG_HIP_FN(upload_nodes_theta(ctx, d_nodes, d_theta, nodes, m, C, W, b));
+    if (k) GG_HIP_FN(hipMemcpyAsync(d_k.p, k, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream));
+    if (lds > 48 * 1024) GG_HIP_FN(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((unsigned)std::min<int64_t>(1024, (m + 3) / 4));
     const float *E = ctx->model[which].E, *dW = d_theta.as<float>(), *db = dW + cd;
     if (ml) {
@@ -869,10 +714,10 @@ int predict_call(gg_ctx *ctx, const char *fn, bool ml, int which, const int32_t 
         hipLaunchKernelGGL(nc_predict_kernel, grid, dim3(256), lds, ctx->stream, E, ld, d, d_nodes.as<int32_t>(), m, C, dW, db, d_pred.as<int32_t>(),
                            d_logits.as<float>());
     }
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(pred_out, d_pred.p, pred_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (logits_out) NC_HIP(hipMemcpyAsync(logits_out, d_logits.p, logit_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipGetLastError());
+    GG_HIP_FN(hipMemcpyAsync(pred_out, d_pred.p, pred_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits_out) GG_HIP_FN(hipMemcpyAsync(logits_out, d_logits.p, logit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 
@@ -886,15 +731,15 @@ EdgePlan edge_plan(int64_t m, int ld, int max_grid) {
 }
 
 // device state of an edge fit or loss-and-gradient call; theta = (w [d], b [1])
-struct EdgeFit {
-    ScopedBuf u, v, y, theta, mom, var, grad, part, loss;
+struct EdgeFit : AdamBufs {
+    ScopedBuf u, v, y, part;
 };
 
 int check_edges(gg_ctx *ctx, const char *fn, int which, int op, const int32_t *u, const int32_t *v, int64_t m) {
     GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator), got %d", fn, which);
     GG_CHECK(ctx, op >= 0 && op <= 3, GG_EINVAL, "%s: op = %d outside [0, 3] (0 Hadamard, 1 average, 2 L1, 3 L2)", fn, op);
     GG_CHECK(ctx, m >= 1 && m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld outside [1, 2^31 - 1]", fn, (long long)m);
-    GG_CHECK(ctx, ctx->n_emb <= NC_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, NC_MAX_D, ctx->n_emb);
+    GG_CHECK(ctx, ctx->n_emb <= RT_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, RT_MAX_D, ctx->n_emb);
     GG_CHECK(ctx, u != nullptr, GG_EINVAL, "%s: u is NULL", fn);
     GG_CHECK(ctx, v != nullptr, GG_EINVAL, "%s: v is NULL", fn);
     for (int64_t i = 0; i < m; ++i) {
@@ -947,15 +792,15 @@ int edge_lossgrad_call(gg_ctx *ctx, int which, int op, const int32_t *u, const i
     const size_t d = ctx->n_emb;
     const EdgePlan p = edge_plan(m, ctx->ld, EC_MAX_GRID);
     EdgeFit f;
-    NC_HIP(f.grad.reserve(sizeof(float) * (d + 2)));
-    NC_HIP(f.part.reserve(sizeof(float) * (d + 3) * p.grid));
-    NC_HIP(edge_upload(ctx, f, u, v, y, m, w, b));
+    GG_HIP_FN(f.grad.reserve(sizeof(float) * (d + 2)));
+    GG_HIP_FN(f.part.reserve(sizeof(float) * (d + 3) * p.grid));
+    GG_HIP_FN(edge_upload(ctx, f, u, v, y, m, w, b));
     enqueue_edge_lossgrad(ctx, f, p, which, op, m, l2, nullptr);
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(gw_out, f.grad.p, sizeof(float) * d, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(gb_out, f.grad.as<float>() + d, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(loss_out, f.grad.as<float>() + d + 1, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipGetLastError());
+    GG_HIP_FN(hipMemcpyAsync(gw_out, f.grad.p, sizeof(float) * d, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(gb_out, f.grad.as<float>() + d, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(loss_out, f.grad.as<float>() + d + 1, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 
@@ -970,36 +815,18 @@ int edge_fit_call(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_
     GG_CHECK(ctx, lr > 0.f && std::isfinite(lr), GG_EINVAL, "%s: lr must be finite and > 0", fn);
     GG_CHECK(ctx, l2 >= 0.f && std::isfinite(l2), GG_EINVAL, "%s: l2 must be finite and >= 0", fn);
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t d = ctx->n_emb, n_par = d + 1;
+    const size_t d = ctx->n_emb;
     const EdgePlan p = edge_plan(m, ctx->ld, EC_MAX_GRID);
     EdgeFit f;
-    NC_HIP(f.grad.reserve(sizeof(float) * (n_par + 1)));
-    NC_HIP(f.part.reserve(sizeof(float) * (n_par + 2) * p.grid));
-    NC_HIP(f.mom.reserve(sizeof(float) * n_par));
-    NC_HIP(f.var.reserve(sizeof(float) * n_par));
-    NC_HIP(f.loss.reserve(sizeof(float) * iters));
-    NC_HIP(edge_upload(ctx, f, u, v, y, m, w_inout, b_inout));
-    NC_HIP(hipMemsetAsync(f.mom.p, 0, sizeof(float) * n_par, ctx->stream));
-    NC_HIP(hipMemsetAsync(f.var.p, 0, sizeof(float) * n_par, ctx->stream));
-    (void)hipEventRecord(ctx->ev0, ctx->stream);
-    double b1p = 1.0, b2p = 1.0;
-    for (int t = 0; t < iters; ++t) {
-        b1p *= 0.9;
-        b2p *= 0.999;
-        enqueue_edge_lossgrad(ctx, f, p, which, op, m, l2, f.loss.as<float>() + t);
-        hipLaunchKernelGGL(nc_adam_kernel, dim3(cdiv(n_par, 256)), dim3(256), 0, ctx->stream, f.theta.as<float>(), f.mom.as<float>(), f.var.as<float>(),
-                           f.grad.as<float>(), (int64_t)n_par, lr, (float)(1.0 - b1p), (float)(1.0 - b2p));
-    }
-    (void)hipEventRecord(ctx->ev1, ctx->stream);
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(w_inout, f.theta.p, sizeof(float) * d, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipMemcpyAsync(b_inout, f.theta.as<float>() + d, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (loss_out) NC_HIP(hipMemcpyAsync(loss_out, f.loss.p, sizeof(float) * iters, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    if (ms_out) *ms_out = ms;
-    return GG_OK;
+    auto upload = [&] {
+        hipError_t e = f.grad.reserve(sizeof(float) * (d + 2));
+        if (e == hipSuccess) e = f.part.reserve(sizeof(float) * (d + 3) * p.grid);
+        if (e == hipSuccess) e = edge_upload(ctx, f, u, v, y, m, w_inout, b_inout);
+        return e;
+    };
+    return adam_fit(
+        ctx, fn, f, d, 1, iters, lr, upload, [&](float *loss_dev) { enqueue_edge_lossgrad(ctx, f, p, which, op, m, l2, loss_dev); }, w_inout, b_inout,
+        loss_out, ms_out);
 }
 
 int edge_predict_call(gg_ctx *ctx, int which, int op, const int32_t *u, const int32_t *v, int64_t m, const float *w, const float *b, float *logits_out) {
@@ -1012,14 +839,14 @@ int edge_predict_call(gg_ctx *ctx, int which, int op, const int32_t *u, const in
     const EdgePlan p = edge_plan(m, ctx->ld, EC_PREDICT_GRID);
     EdgeFit f;
     ScopedBuf d_logits;
-    NC_HIP(d_logits.reserve(sizeof(float) * (size_t)m));
-    NC_HIP(edge_upload(ctx, f, u, v, nullptr, m, w, b));
+    GG_HIP_FN(d_logits.reserve(sizeof(float) * (size_t)m));
+    GG_HIP_FN(edge_upload(ctx, f, u, v, nullptr, m, w, b));
     EdgeArgs a{ctx->model[which].E, f.u.as<int32_t>(), f.v.as<int32_t>(), nullptr, m, ctx->ld, d, f.theta.as<float>(), f.theta.as<float>() + d, nullptr,
                d_logits.as<float>()};
     hipLaunchKernelGGL(ec_predicts[op][p.NJ - 1], dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    NC_HIP(hipGetLastError());
-    NC_HIP(hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    NC_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipGetLastError());
+    GG_HIP_FN(hipMemcpyAsync(logits_out, d_logits.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 

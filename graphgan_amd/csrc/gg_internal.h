@@ -36,6 +36,15 @@ struct DevBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+// A device allocation that lives as long as one call: released when the call returns, on every path -- behind the stream
+// synchronisation, or behind the HIP call that failed.
+struct ScopedBuf : DevBuf {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf &) = delete;
+    ScopedBuf &operator=(const ScopedBuf &) = delete;
+    ~ScopedBuf() { release(); }
+};
+
 // One embedding model (generator or discriminator): table, bias, Adam slots.
 struct Model {
     float *E = nullptr, *b = nullptr;      // [n_node * ld], [n_node]
@@ -327,6 +336,14 @@ int fail(gg_ctx *ctx, int code, const char *fmt, ...);
         if (e__ != hipSuccess)                                                                 \
             return gg::fail(ctx, GG_EHIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call,         \
                             hipGetErrorString(e__));                                           \
+    } while (0)
+
+// A HIP call of the entry point named by the enclosing function's `fn` (with its `ctx`): its failure ends the call with the
+// entry point's name in the error text.
+#define GG_HIP_FN(call)                                                                            \
+    do {                                                                                           \
+        const hipError_t e__ = (call);                                                             \
+        if (e__ != hipSuccess) return gg::fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e__)); \
     } while (0)
 
 #define GG_CHECK(ctx, cond, code, ...)                        \

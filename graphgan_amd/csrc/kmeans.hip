@@ -2,23 +2,17 @@
 //     a_i = argmin_c |x_i - c_c|^2 = argmin_c g_ic,   g_ic = h_c - x_i . c_c,   h_c = |c_c|^2 / 2     (ties: the lowest c)
 //     dist2_i = max(0, |x_i|^2 + 2 g_{i, a_i}),   inertia = sum_i dist2_i
 //     S_c = sum_{a_i = c} x_i,   n_c = |{i : a_i = c}|,   c_c <- S_c / n_c   (an empty cluster keeps its centroid)
-// km_sweep_kernel is the hot path and has the data flow of the classifier's sweep (classifier.hip, nc_sweep_kernel): a
-// persistent workgroup (256 threads, 4 wavefronts) walks 64-row tiles; per tile
-//   1. the rows are gathered into LDS (Xs; the next tile's rows are already in flight to registers while this one computes),
-//   2. D[64, k] = Xs . Cs^T on v_mfma_f32_32x32x2_f32, the centroids staged in LDS (Cs) once per workgroup -- in k-chunks per
-//      tile only where k x d does not fit beside the tile (km_plan: the classifier's six (CT, DT) instances),
-//   3. per row, by 4 threads: |x_i|^2, the argmin of h_c - D_ic over c < k, dist2_i; the row's assignment and distance are
-//      written out, the inertia term goes to a float64 accumulator, `changed` counts a_i != the previous assignment,
-//   4. P = onehot(a_i) left in LDS (Ps; zero rows behind M, zero columns behind k),
-//   5. S[k, d] += P^T . Xs on the same matrix instruction, the accumulators in registers across all tiles of the workgroup;
-//      n_c += column sums of P, as integers.
+// km_sweep_kernel is the hot path: the row-tile sweep of row_tiles.h (gather, D = Xs . Cs^T with the centroids as the staged
+// operand, row stage, S += P^T . Xs; the geometry, the barriers and the launch plan are described there) with this file's row
+// stage: per row, by 4 threads, |x_i|^2, the argmin of h_c - D_ic over c < k, dist2_i; the row's assignment and distance are
+// written out, the inertia term goes to a float64 accumulator, `changed` counts a_i != the previous assignment; P = onehot(a_i)
+// is left in LDS; n_c += column sums of P, as integers.
 // The factors of the second product are 0 and 1: the matrix instruction is a k-ordered chain of fmaf, and fmaf(1, x, s) = s + x,
 // fmaf(0, x, s) = s exactly, so S_c is the plain float32 sum of the cluster's rows in tile order -- no product is ever rounded.
-// SUMS = false drops steps 4 and 5 (the assign-only calls: distances for seeding); steps 1 - 3 are the same code, the same bits.
-// CT = ceil(k / 32) and DT = ceil(ld / 32) are template parameters: an instantiation that spills fails the build.
-// Determinism: the grid is min(KM_MAX_GRID, ceil(M / 64)) -- a function of M alone --, tiles go to workgroups round robin, every
-// workgroup writes its partial (sums [k d] + the inertia as (high, remainder) floats; counts [k] + changed as integers) to a
-// stage and km_update_kernel adds the stage in a fixed order.  No floating-point atomics: the same inputs give the same bits.
+// SUMS = false drops P, the counts and the second product (the assign-only calls: distances for seeding); the rest is the same
+// code, the same bits.
+// Every workgroup writes its partial (sums [k d] + the inertia as (high, remainder) floats; counts [k] + changed as integers) to
+// a stage and km_update_kernel adds the stage in a fixed order.  No floating-point atomics: the same inputs give the same bits.
 // km_update_kernel also applies the centroid update of a fit and owns its stop rule: ctl[0] = the sweep number the fit stopped
 // at (0 while it runs), ctl[1] = converged.  A sweep or update of a later iteration finds ctl[0] set and returns at once, so all
 // max_iters iterations are enqueued behind one another and the host synchronises once.
@@ -26,22 +20,13 @@
 
 #include <algorithm>
 
-#include "gg_internal.h"
+#include "row_tiles.h"
 
 namespace gg {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int KM_RT = 64;           // rows per tile
-constexpr int KM_MAX_GRID = 512;    // workgroups of a sweep, at most
-constexpr int KM_MAX_K = 128, KM_MAX_D = 256;
-constexpr size_t KM_LDS = 150 * 1024;  // dynamic LDS of a sweep workgroup, at most
 constexpr int KM_RED_COLS = 32, KM_RED_SLICES = 8;  // km_update_kernel: entries x stage slices per workgroup
-
-// C/D layout of v_mfma_f32_32x32x2_f32 (score_tiles.h, tile_row)
-__device__ __forceinline__ int km_tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // has a fit stopped before iteration t?  (ctl[0] = the sweep it stopped at; the update kernel of sweep t itself may see t)
 __device__ __forceinline__ bool km_stopped(const int32_t *ctl, int t) {
@@ -67,55 +52,19 @@ struct KmArgs {
 
 template <int CT, int DT, bool SUMS>
 __global__ __launch_bounds__(256) void km_sweep_kernel(KmArgs a) {
-    constexpr int XS = 32 * DT + 1, PS = 32 * CT + 1;       // row strides of Xs / Ps (odd: conflict-free column walks)
-    constexpr int N1 = (2 * CT + 3) / 4;                     // distance tiles (row half, cluster tile) per wavefront
-    constexpr int N2 = SUMS ? (CT * DT + 3) / 4 : 1;         // sum tiles (cluster tile, column tile) per wavefront
-    constexpr int NPF = 2 * DT;                              // float4 pieces of a tile per thread
+    constexpr int XS = RowTiles<CT, DT>::XS, PS = RowTiles<CT, DT>::PS;
     extern __shared__ float km_lds[];
-    __shared__ float hs[KM_MAX_K];  // h_c = |c_c|^2 / 2
+    __shared__ float hs[RT_MAX_OUT];  // h_c = |c_c|^2 / 2
     __shared__ double red[256];     // the workgroup's inertia terms (float64: a sum of M terms must keep the last digits)
     __shared__ int redi[256];
     if (km_stopped(a.ctl, a.t)) return;
-    float *Xs = km_lds, *Ps = Xs + KM_RT * XS, *Cs = Ps + KM_RT * PS;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const int ld = a.ld, d = a.d, k = a.k, KW = a.KW, WS = KW + 1;
-    const bool c_resident = KW >= ld;
-    const int64_t n_tiles = (a.m + KM_RT - 1) / KM_RT;
-
-    auto stage_c = [&](int k0) {
-        const int kw = min(KW, ld - k0);
-        for (int i = tid; i < 32 * CT * kw; i += 256) {
-            const int c = i / kw, kk = i - c * kw, col = k0 + kk;
-            Cs[c * WS + kk] = (c < k && col < d) ? a.cen[(int64_t)c * d + col] : 0.f;
-        }
-    };
-    float4 pf[NPF];
-    auto fetch = [&](int64_t tile) {  // the tile's rows -> registers (rows behind M and columns behind ld: zeros)
-        const int64_t row0 = tile * KM_RT;
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
-            pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (tile < n_tiles && row0 + r < a.m && col < ld) pf[j] = *(const float4 *)(a.E + (int64_t)a.nodes[row0 + r] * ld + col);
-        }
-    };
-
-    f32x16 acc2[N2];
-#pragma unroll
-    for (int i = 0; i < N2; ++i)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc2[i][q] = 0.f;
+    const int tid = threadIdx.x, d = a.d, k = a.k;
     double inertia_acc = 0.0;
     int cnt_acc = 0, changed_acc = 0;
 
-    fetch(blockIdx.x);
     // h_c: one thread per centroid, columns ascending (the order is part of the result; every workgroup computes the same bits).
     // From the staged copy where it is resident (odd row stride: conflict-free; the padding columns add +0), else from global
     // memory; either way the loads of 8 columns are issued together.
-    if (c_resident) {
-        stage_c(0);
-        __syncthreads();
-    }
     auto half_norm = [&](const float *c, int n) {
         float s = 0.f;
         int j = 0;
@@ -129,176 +78,77 @@ __global__ __launch_bounds__(256) void km_sweep_kernel(KmArgs a) {
         for (; j < n; ++j) s += c[j] * c[j];
         return 0.5f * s;
     };
-    if (tid < k) hs[tid] = c_resident ? half_norm(Cs + tid * WS, ld) : half_norm(a.cen + (int64_t)tid * d, d);  // (ld: a multiple of 4)
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t row0 = tile * KM_RT;
-        __syncthreads();  // the previous tile's sum product has read Xs / Ps
-#pragma unroll
-        for (int j = 0; j < NPF; ++j) {
-            const int i = tid + 256 * j, r = i / (8 * DT), col = (i % (8 * DT)) * 4;
-            float *x = Xs + r * XS + col;
-            x[0] = pf[j].x; x[1] = pf[j].y; x[2] = pf[j].z; x[3] = pf[j].w;
-        }
-        fetch(tile + gridDim.x);
-        if (c_resident) __syncthreads();
+    auto setup = [&](const float *Cs, int WS, bool resident) {
+        if (resident) __syncthreads();
+        if (tid < k) hs[tid] = resident ? half_norm(Cs + tid * WS, a.ld) : half_norm(a.cen + (int64_t)tid * d, d);  // (ld: a multiple of 4)
+    };
 
-        // 2. D = Xs . Cs^T: unit u = wv + 4 i is (row half u & 1, cluster tile u >> 1)
-        f32x16 acc1[N1];
+    // row tid >> 2 by 4 threads (columns / clusters q, q + 4, ...): |x|^2, the argmin with ties to the lowest cluster
+    auto rows = [&](int64_t row0, const float *Xs, float *Ps) {
+        const int r = tid >> 2, q = tid & 3;
+        const bool valid = row0 + r < a.m;
+        float *p = Ps + r * PS;
+        const float *x = Xs + r * XS;
+        // |x|^2: thread q takes columns 32 b + 8 q + j (bank r + 8 q + j: the 32 lanes of a half hit 32 banks; columns behind
+        // ld hold zeros), 8 loads issued together -- one wavefront per SIMD hides no LDS latency behind another
+        float x2 = 0.f;
 #pragma unroll
-        for (int i = 0; i < N1; ++i)
+        for (int b = 0; b < DT; ++b) {
+            float v[8];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) acc1[i][q] = 0.f;
-        for (int k0 = 0; k0 < ld; k0 += KW) {
-            if (!c_resident) {
-                __syncthreads();
-                stage_c(k0);
-                __syncthreads();
+            for (int j = 0; j < 8; ++j) v[j] = x[32 * b + 8 * q + j];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x2 += v[j] * v[j];
+        }
+        x2 += __shfl_xor(x2, 1);
+        x2 += __shfl_xor(x2, 2);
+        float best = INFINITY;
+        int bc = 0x7fffffff;
+#pragma unroll
+        for (int b = 0; b < CT; ++b) {  // (the thread's clusters ascend: a later equal score does not replace)
+            float g[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int c = 32 * b + q + 4 * j;  // (hs has RT_MAX_OUT entries and Ps 32 CT columns: every load is in bounds)
+                const float hv = hs[c], pv = p[c];
+                g[j] = c < k ? hv - pv : INFINITY;
             }
-            const int kmax = min(KW, ld - k0);
 #pragma unroll
-            for (int i = 0; i < N1; ++i) {
-                const int u = wv + 4 * i;
-                if (u < 2 * CT) {
-                    const float *xa = Xs + ((u & 1) * 32 + l31) * XS + k0 + half;
-                    const float *cb = Cs + ((u >> 1) * 32 + l31) * WS + half;
-                    int kk = 0;
-                    for (; kk + 16 <= kmax; kk += 16) {  // (8 steps: their 16 LDS reads are issued ahead of the matrix instructions)
-                        float xv[8], cv[8];
-#pragma unroll
-                        for (int s = 0; s < 8; ++s) {
-                            xv[s] = xa[kk + 2 * s];
-                            cv[s] = cb[kk + 2 * s];
-                        }
-#pragma unroll
-                        for (int s = 0; s < 8; ++s) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], cv[s], acc1[i], 0, 0, 0);
-                    }
-                    for (; kk < kmax; kk += 2) acc1[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[kk], cb[kk], acc1[i], 0, 0, 0);
+            for (int j = 0; j < 8; ++j)
+                if (g[j] < best) {
+                    best = g[j];
+                    bc = 32 * b + q + 4 * j;
                 }
-            }
         }
 #pragma unroll
-        for (int i = 0; i < N1; ++i) {
-            const int u = wv + 4 * i;
-            if (u < 2 * CT) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) Ps[((u & 1) * 32 + km_tile_row(reg, half)) * PS + (u >> 1) * 32 + l31] = acc1[i][reg];
+        for (int o = 1; o < 4; o <<= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int oc = __shfl_xor(bc, o);
+            if (ob < best || (ob == best && oc < bc)) {
+                best = ob;
+                bc = oc;
             }
         }
-        __syncthreads();
-
-        // 3. row tid >> 2 by 4 threads (columns / clusters q, q + 4, ...): |x|^2, the argmin with ties to the lowest cluster
-        {
-            const int r = tid >> 2, q = tid & 3;
-            const bool valid = row0 + r < a.m;
-            float *p = Ps + r * PS;
-            const float *x = Xs + r * XS;
-            // |x|^2: thread q takes columns 32 b + 8 q + j (bank r + 8 q + j: the 32 lanes of a half hit 32 banks; columns behind
-            // ld hold zeros), 8 loads issued together -- one wavefront per SIMD hides no LDS latency behind another
-            float x2 = 0.f;
-#pragma unroll
-            for (int b = 0; b < DT; ++b) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = x[32 * b + 8 * q + j];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) x2 += v[j] * v[j];
-            }
-            x2 += __shfl_xor(x2, 1);
-            x2 += __shfl_xor(x2, 2);
-            float best = INFINITY;
-            int bc = 0x7fffffff;
-#pragma unroll
-            for (int b = 0; b < CT; ++b) {  // (the thread's clusters ascend: a later equal score does not replace)
-                float g[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int c = 32 * b + q + 4 * j;  // (hs has KM_MAX_K entries and Ps 32 CT columns: every load is in bounds)
-                    const float hv = hs[c], pv = p[c];
-                    g[j] = c < k ? hv - pv : INFINITY;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (g[j] < best) {
-                        best = g[j];
-                        bc = 32 * b + q + 4 * j;
-                    }
-            }
-#pragma unroll
-            for (int o = 1; o < 4; o <<= 1) {
-                const float ob = __shfl_xor(best, o);
-                const int oc = __shfl_xor(bc, o);
-                if (ob < best || (ob == best && oc < bc)) {
-                    best = ob;
-                    bc = oc;
-                }
-            }
-            if (bc >= k) bc = 0;  // no score compared below +inf (a row of NaN): cluster 0; nothing outside [0, k) leaves here
-            const float dist2 = fmaxf(0.f, x2 + 2.f * best);
-            if (q == 0 && valid) {
-                inertia_acc += (double)dist2;
-                if (a.has_prev) changed_acc += a.assign[row0 + r] != bc ? 1 : 0;
-                if (a.assign) a.assign[row0 + r] = bc;
-                if (a.dist2) a.dist2[row0 + r] = dist2;
-            }
-            // 4. P = onehot(a_i): every thread rewrites the columns it has read
-            if constexpr (SUMS)
-                for (int c = q; c < 32 * CT; c += 4) p[c] = (valid && c == bc) ? 1.f : 0.f;
+        if (bc >= k) bc = 0;  // no score compared below +inf (a row of NaN): cluster 0; nothing outside [0, k) leaves here
+        const float dist2 = fmaxf(0.f, x2 + 2.f * best);
+        if (q == 0 && valid) {
+            inertia_acc += (double)dist2;
+            if (a.has_prev) changed_acc += a.assign[row0 + r] != bc ? 1 : 0;
+            if (a.assign) a.assign[row0 + r] = bc;
+            if (a.dist2) a.dist2[row0 + r] = dist2;
         }
-
-        // 5. sums: tile t = wv + 4 i is (cluster tile t / DT, column tile t % DT); k runs over the 64 rows
-        if constexpr (SUMS) {
-            __syncthreads();
-            if (tid < k) {
-#pragma unroll 8
-                for (int r = 0; r < KM_RT; ++r) cnt_acc += Ps[r * PS + tid] != 0.f ? 1 : 0;
-            }
-#pragma unroll
-            for (int i = 0; i < N2; ++i) {
-                const int t = wv + 4 * i;
-                if (t < CT * DT) {
-                    const float *pa = Ps + half * PS + (t / DT) * 32 + l31;
-                    const float *xb = Xs + half * XS + (t % DT) * 32 + l31;
-#pragma unroll 8
-                    for (int kk = 0; kk < KM_RT; kk += 2) acc2[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[kk * PS], xb[kk * XS], acc2[i], 0, 0, 0);
-                }
-            }
-        }
-    }
-
+        // P = onehot(a_i): every thread rewrites the columns it has read
+        if constexpr (SUMS)
+            for (int c = q; c < 32 * CT; c += 4) p[c] = (valid && c == bc) ? 1.f : 0.f;
+    };
+    auto column = [&](float p) { cnt_acc += p != 0.f ? 1 : 0; };
     // the workgroup's partial
     float *part = a.part_f + (int64_t)blockIdx.x * ((int64_t)k * d + 2);
     int32_t *parti = a.part_i + (int64_t)blockIdx.x * (k + 1);
-    if constexpr (SUMS) {
-#pragma unroll
-        for (int i = 0; i < N2; ++i) {
-            const int t = wv + 4 * i;
-            if (t < CT * DT) {
-                const int col = (t % DT) * 32 + l31;
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int c = (t / DT) * 32 + km_tile_row(reg, half);
-                    if (c < k && col < d) part[(int64_t)c * d + col] = acc2[i][reg];
-                }
-            }
-        }
+    row_tile_sweep<CT, DT, SUMS>(km_lds, a.E, a.nodes, a.m, a.ld, d, k, a.cen, a.KW, part, setup, rows, column);
+    if constexpr (SUMS)
         if (tid < k) parti[tid] = cnt_acc;
-    }
-    red[tid] = inertia_acc;
-    redi[tid] = changed_acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) {
-            red[tid] += red[tid + w];
-            redi[tid] += redi[tid + w];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float hi = (float)red[0];
-        part[(int64_t)k * d] = hi;
-        part[(int64_t)k * d + 1] = (float)(red[0] - (double)hi);
-        parti[k] = redi[0];
-    }
+    rt_block_sum(red, inertia_acc, part + (int64_t)k * d, redi, changed_acc, parti + k);
 }
 
 // The totals of a sweep from its stage, and -- in a fit (max_iters > 0) -- the centroid update and the stop rule.
@@ -398,40 +248,15 @@ typedef void (*KmFn)(KmArgs);
 const KmFn km_sweeps[2][4][8] = {{KM_ROW(1, false), KM_ROW(2, false), KM_ROW(3, false), KM_ROW(4, false)},
                                  {KM_ROW(1, true), KM_ROW(2, true), KM_ROW(3, true), KM_ROW(4, true)}};
 
-// The launch plan of a sweep (the classifier's sweep_plan): template instance, grid (a function of m alone), dynamic LDS and the
-// centroid k-chunk.
-struct KmPlan {
+// The launch plan of a sweep (row_tiles.h) with its template instance
+struct KmPlan : RowTilePlan {
     KmFn fn;
-    int grid, KW;
-    size_t lds;
 };
 
 KmPlan km_plan(int64_t m, int k, int ld, bool with_sums) {
-    const int CT = cdiv(k, 32), DT = cdiv(ld, 32);
-    const size_t fixed = sizeof(float) * KM_RT * ((size_t)(32 * DT + 1) + (32 * CT + 1));
-    int KW = (int)((KM_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;
-    KW = KW >= ld ? ld : (KW / 4) * 4;
-    KmPlan p;
-    p.fn = km_sweeps[with_sums ? 1 : 0][CT - 1][DT - 1];
-    p.grid = (int)std::min<int64_t>(KM_MAX_GRID, (m + KM_RT - 1) / KM_RT);
-    p.KW = KW;
-    p.lds = fixed + sizeof(float) * 32 * CT * (size_t)(KW + 1);
-    return p;
+    const RowTilePlan t = row_tile_plan(m, k, ld);
+    return KmPlan{t, km_sweeps[with_sums ? 1 : 0][t.CT - 1][t.DT - 1]};
 }
-
-// A device allocation that lives as long as one call: released when the call returns, on every path.
-struct ScopedBuf : DevBuf {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf &) = delete;
-    ScopedBuf &operator=(const ScopedBuf &) = delete;
-    ~ScopedBuf() { release(); }
-};
-
-#define KM_HIP(call)                                                                           \
-    do {                                                                                       \
-        const hipError_t e__ = (call);                                                         \
-        if (e__ != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e__)); \
-    } while (0)
 
 // device state of a step or fit call
 struct KmState {
@@ -439,14 +264,10 @@ struct KmState {
 };
 
 int km_check(gg_ctx *ctx, const char *fn, int which, const int32_t *nodes, int64_t m, int k) {
-    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator), got %d", fn, which);
-    GG_CHECK(ctx, k >= 1 && k <= KM_MAX_K, GG_EINVAL, "%s: k = %d outside [1, %d]", fn, k, KM_MAX_K);
-    GG_CHECK(ctx, m >= 1 && m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld outside [1, 2^31 - 1]", fn, (long long)m);
-    GG_CHECK(ctx, ctx->n_emb <= KM_MAX_D, GG_EINVAL, "%s: supports n_emb <= %d (got %d)", fn, KM_MAX_D, ctx->n_emb);
-    GG_CHECK(ctx, nodes != nullptr, GG_EINVAL, "%s: nodes is NULL", fn);
-    for (int64_t i = 0; i < m; ++i)
-        GG_CHECK(ctx, nodes[i] >= 0 && nodes[i] < ctx->n_node, GG_EINVAL, "%s: node id %d (entry %lld) outside [0, %d)", fn, nodes[i], (long long)i, ctx->n_node);
-    return GG_OK;
+    return check_rows(ctx, fn, which, nodes, m, [&] {
+        GG_CHECK(ctx, k >= 1 && k <= RT_MAX_OUT, GG_EINVAL, "%s: k = %d outside [1, %d]", fn, k, RT_MAX_OUT);
+        return (int)GG_OK;
+    });
 }
 
 int km_check_ids(gg_ctx *ctx, const char *fn, const char *name, const int32_t *ids, int k) {
@@ -511,15 +332,15 @@ int step_call(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int k, co
     const bool with_sums = sums_out || counts_out;
     const KmPlan p = km_plan(m, k, ctx->ld, with_sums);
     KmState s;
-    KM_HIP(km_upload(ctx, s, p, which, nodes, m, k, centroids, centroid_nodes, assign_out != nullptr, dist2_out != nullptr, 1));
+    GG_HIP_FN(km_upload(ctx, s, p, which, nodes, m, k, centroids, centroid_nodes, assign_out != nullptr, dist2_out != nullptr, 1));
     km_enqueue(ctx, s, p, with_sums, which, m, k, 1, 0, s.inertia.as<double>());
-    KM_HIP(hipGetLastError());
-    if (assign_out) KM_HIP(hipMemcpyAsync(assign_out, s.assign.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (dist2_out) KM_HIP(hipMemcpyAsync(dist2_out, s.dist2.p, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (sums_out) KM_HIP(hipMemcpyAsync(sums_out, s.sums.p, sizeof(float) * kd, hipMemcpyDeviceToHost, ctx->stream));
-    if (counts_out) KM_HIP(hipMemcpyAsync(counts_out, s.counts.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
-    if (inertia_out) KM_HIP(hipMemcpyAsync(inertia_out, s.inertia.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    KM_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipGetLastError());
+    if (assign_out) GG_HIP_FN(hipMemcpyAsync(assign_out, s.assign.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist2_out) GG_HIP_FN(hipMemcpyAsync(dist2_out, s.dist2.p, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (sums_out) GG_HIP_FN(hipMemcpyAsync(sums_out, s.sums.p, sizeof(float) * kd, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts_out) GG_HIP_FN(hipMemcpyAsync(counts_out, s.counts.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
+    if (inertia_out) GG_HIP_FN(hipMemcpyAsync(inertia_out, s.inertia.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     return GG_OK;
 }
 
@@ -536,22 +357,22 @@ int fit_call(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int k, int
     const size_t kd = (size_t)k * ctx->n_emb;
     const KmPlan p = km_plan(m, k, ctx->ld, true);
     KmState s;
-    KM_HIP(km_upload(ctx, s, p, which, nodes, m, k, centroids_inout, init_nodes, true, dist2_out != nullptr, max_iters));
+    GG_HIP_FN(km_upload(ctx, s, p, which, nodes, m, k, centroids_inout, init_nodes, true, dist2_out != nullptr, max_iters));
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     for (int t = 1; t <= max_iters; ++t) km_enqueue(ctx, s, p, true, which, m, k, t, max_iters, s.inertia.as<double>() + (t - 1));
     (void)hipEventRecord(ctx->ev1, ctx->stream);
-    KM_HIP(hipGetLastError());
+    GG_HIP_FN(hipGetLastError());
     int32_t ctl[2] = {0, 0};
-    KM_HIP(hipMemcpyAsync(ctl, s.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
-    KM_HIP(hipMemcpyAsync(centroids_inout, s.cen.p, sizeof(float) * kd, hipMemcpyDeviceToHost, ctx->stream));
-    if (assign_out) KM_HIP(hipMemcpyAsync(assign_out, s.assign.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (dist2_out) KM_HIP(hipMemcpyAsync(dist2_out, s.dist2.p, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (counts_out) KM_HIP(hipMemcpyAsync(counts_out, s.counts.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
-    KM_HIP(hipStreamSynchronize(ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(ctl, s.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipMemcpyAsync(centroids_inout, s.cen.p, sizeof(float) * kd, hipMemcpyDeviceToHost, ctx->stream));
+    if (assign_out) GG_HIP_FN(hipMemcpyAsync(assign_out, s.assign.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist2_out) GG_HIP_FN(hipMemcpyAsync(dist2_out, s.dist2.p, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts_out) GG_HIP_FN(hipMemcpyAsync(counts_out, s.counts.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     GG_CHECK(ctx, ctl[0] >= 1 && ctl[0] <= max_iters, GG_EHIP, "%s: the device reported %d sweeps of at most %d", fn, ctl[0], max_iters);
     if (inertia_out) {  // the sweeps that ran; later entries are not written
-        KM_HIP(hipMemcpyAsync(inertia_out, s.inertia.p, sizeof(double) * ctl[0], hipMemcpyDeviceToHost, ctx->stream));
-        KM_HIP(hipStreamSynchronize(ctx->stream));
+        GG_HIP_FN(hipMemcpyAsync(inertia_out, s.inertia.p, sizeof(double) * ctl[0], hipMemcpyDeviceToHost, ctx->stream));
+        GG_HIP_FN(hipStreamSynchronize(ctx->stream));
     }
     if (iters_out) *iters_out = ctl[0];
     if (converged_out) *converged_out = ctl[1];

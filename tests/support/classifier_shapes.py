@@ -1,5 +1,5 @@
 """What tests/test_gpu_classifier_shapes.py and tests/test_classifier_shapes_cpu.py share: a plain-Python restatement of the
-sweep's launch plan (graphgan_amd/csrc/classifier.hip, sweep_plan), the case lists, integer tables with the closed forms of the
+sweep's launch plan (graphgan_amd/csrc/row_tiles.h, row_tile_plan), the case lists, integer tables with the closed forms of the
 sweep's outputs at W = 0, b = 0, l2 = 0, and label generators.
 
 Exact row accounting.  With table entries in {-1, 0, 1} and zero parameters every logit is 0: softmax gives p = 1 / C per class
@@ -12,7 +12,7 @@ correctly rounded division away from integers:
 tile read from stale LDS or a partial summed twice changes an integer numerator and with it the bits."""
 import numpy as np
 
-NC_RT, NC_MAX_GRID, NC_LDS = 64, 512, 150 * 1024  # rows per tile, workgroups at most, dynamic LDS at most (classifier.hip)
+NC_RT, NC_MAX_GRID, NC_LDS = 64, 512, 150 * 1024  # rows per tile, workgroups at most, dynamic LDS at most (row_tiles.h)
 N_TABLE = 5000
 
 
@@ -26,7 +26,7 @@ def ld_of(d):
 
 
 def sweep_plan(C, ld):
-    """classifier.hip's sweep_plan for C classes at row stride ld -> dict(CT, DT, KW, chunks, lds): the template instance, the
+    """row_tiles.h's row_tile_plan for C classes at row stride ld -> dict(CT, DT, KW, chunks, lds): the template instance, the
     k-chunk of the W staging (== ld: W is staged once per workgroup), the column counts of the chunks, the dynamic LDS bytes"""
     CT, DT = cdiv(C, 32), cdiv(ld, 32)
     fixed = 4 * NC_RT * ((32 * DT + 1) + (32 * CT + 1))

@@ -24,14 +24,14 @@ def test_restated_plan_names_the_six_chunked_instances():
     assert set(chunked) == cs.CHUNKED
     assert chunked == {(4, 5): [152, 8], (4, 6): [136, 56], (4, 7): [120, 104], (4, 8): [104, 104, 48], (3, 7): [184, 40],
                        (3, 8): [160, 96]}
-    # drift guard: the restatement copies these constants and these lines of sweep_plan from the kernel file.  If this fails
-    # after an edit of classifier.hip, the plan may have changed: update tests/support/classifier_shapes.py (or, after a mere
-    # reformat, the texts below)
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graphgan_amd", "csrc", "classifier.hip")).read()
-    for text in ("constexpr int NC_RT = 64;", "constexpr int NC_MAX_GRID = 512;", "constexpr size_t NC_LDS = 150 * 1024;",
-                 "int KW = (int)((NC_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;", "KW = KW >= ld ? ld : (KW / 4) * 4;",
-                 "const size_t fixed = sizeof(float) * NC_RT * ((size_t)(32 * DT + 1) + (32 * CT + 1));"):
-        assert text in src, "classifier.hip no longer contains %r: restate sweep_plan in tests/support/classifier_shapes.py" % text
+    # drift guard: the restatement copies these constants and these lines of row_tile_plan from the header the classifier's and
+    # the k-means sweep share.  If this fails after an edit of row_tiles.h, the plan may have changed: update
+    # tests/support/classifier_shapes.py (or, after a mere reformat, the texts below)
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graphgan_amd", "csrc", "row_tiles.h")).read()
+    for text in ("constexpr int RT_ROWS = 64;", "constexpr int RT_MAX_GRID = 512;", "constexpr size_t RT_LDS = 150 * 1024;",
+                 "int KW = (int)((RT_LDS - fixed) / (sizeof(float) * 32 * CT)) - 1;", "KW = KW >= ld ? ld : (KW / 4) * 4;",
+                 "const size_t fixed = sizeof(float) * RT_ROWS * ((size_t)(32 * DT + 1) + (32 * CT + 1));"):
+        assert text in src, "row_tiles.h no longer contains %r: restate row_tile_plan in tests/support/classifier_shapes.py" % text
 
 
 def test_cases_reach_every_instance_and_every_path():

@@ -1,5 +1,5 @@
-"""The classifier's sweep (graphgan_amd/csrc/classifier.hip, nc_sweep_kernel<CT, DT, ML>) at the shapes its launch plan makes
-different: every one of the 64 template instances, the six whose W is staged in k-chunks, more tiles than workgroups (the
+"""The classifier's sweep (graphgan_amd/csrc/classifier.hip, nc_sweep_kernel<CT, DT, ML>) at the shapes its launch plan
+(graphgan_amd/csrc/row_tiles.h, row_tile_plan) makes different: every one of the 64 template instances, the six whose W is staged in k-chunks, more tiles than workgroups (the
 persistent loop, the prefetch, the accumulators carried across tiles, a 512-partial stage), the predict kernels above 48 KiB of
 LDS with a row loop of three trips, and saturated softmax logits.
 

@@ -1,6 +1,6 @@
 """k-means on the device (graphgan_amd/csrc/kmeans.hip: gg_kmeans_step / gg_kmeans_fit, Engine.kmeans_*) and the NodeClusterEval
-evaluator on an engine, at the smallest shapes at which the sweep can go wrong (tests/support/classifier_shapes.py: every
-(CT, DT) instance, ragged edges, more tiles than workgroups).
+evaluator on an engine, at the smallest shapes at which the sweep can go wrong (tests/support/classifier_shapes.py restates the
+launch plan the sweep shares with the classifier's, graphgan_amd/csrc/row_tiles.h, row_tile_plan: every (CT, DT) instance, ragged edges, more tiles than workgroups).
 
 Three kinds of comparison.  EXACT: on tables of {-1, 0, 1} with table rows as centroids every dot product, h_c (a multiple of
 1/2, at most 128), score, dist2, sum (|value| < 2^24) and the inertia is an integer or half-integer, exact in float32 in any
