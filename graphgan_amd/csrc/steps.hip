@@ -1009,162 +1009,221 @@ __global__ __launch_bounds__(256) void sparse_opt_kernel(const OptArgs a) {
 }
 
 // Small rows of the staged gradient: one 16-lane group per row sums the row's segment of the stage buffer (contiguous
-// 512-byte rows, four in flight) and applies lazy Adam (MODE 0) / SGD (MODE 1) with the sum in registers.
+// rows of ld floats, four in flight) and applies lazy Adam (MODE 0) / SGD (MODE 1) with the sum in registers.
 // ORDER OF THE SUM: the position of a gradient row inside its segment is the arrival order of the counting atomics
 // (path_count_kernel / pair_occ_count_kernel) and changes from run to run, so the group first ranks the segment's source
-// keys (stage_key: path position resp. pair side, unique inside a pass) -- segments of <= STAGE_SORT rows by counting
-// smaller keys with shuffles (16 shuffles per 16 keys), the permutation goes through 256 B of LDS per group; longer
-// segments (only with GG_STAGE_T > 64) by repeated minimum selection -- and adds the rows in ASCENDING KEY ORDER: the same
-// fp32 operation sequence in every run, whatever the scheduling was.
+// keys (stage_key: path position resp. pair side, unique inside a pass) by counting smaller keys with shuffles and adds the
+// rows in ASCENDING KEY ORDER: the same fp32 operation sequence in every run, whatever the scheduling was.  Segments of
+// <= 16 rows (one key per lane) invert the ranking with one lane permute; up to STAGE_SORT rows the permutation goes
+// through 256 B of LDS per group; longer segments (only with GG_STAGE_T > 64) use repeated minimum selection.
 // MODE 2 (replicas): the sum goes to the gradient accumulators instead -- plain stores, the row's flag set -- and the
 // exchange + sparse_opt_kernel path takes it from there like an atomically accumulated gradient.
+//
+// A row is a chain of round trips to memory, kept short here -- the list entry; everything whose address follows from it; the
+// ranked stage rows; the stores -- and ONE GROUP TAKES ONE ROW: the dispatcher hands out rows as workgroups retire, which
+// measured faster than any grid-stride loop over the list (profiles/HISTORY.md, "Staged optimizer, pipelined").
+//   * NC, the float4 chunks per lane, is a template parameter and every load is UNCONDITIONAL from a clamped address (the
+//     row's last chunk for the lanes and chunks behind its end, the segment's last row / key behind the segment's end):
+//     no branch between a load and its use, so all chunks of a batch of four stage rows are requested together and waited
+//     for once.  What a clamped load returns is masked where it is used: a select against +0.f -- exact, a sum that
+//     started at +0.f is never -0.f and x + (+0.f) == x for every other x -- or simply never stored.
+//   * With the list entry {row, first stage row, n} in hand the group requests the first key per lane and, for NC <= 2,
+//     the row's E / m / v chunks and b / mb / vb BEFORE it sums the segment: nobody else writes those rows during this
+//     kernel (every table row appears once in the list, hub rows are updated by a later kernel).  The NC = 4 instance
+//     (ld > 128) cannot hold 48 more registers next to a batch of 4 x 4 float4 at its occupancy: it requests the table
+//     chunks behind the sum, all at once.
+//   * n = 1, the commonest row: no keys, no ranking, no LDS; the stage row and its bias word go out with the table rows.
 constexpr int STAGE_SORT = 64;
 
-template <int MODE>
+template <int MODE, int NC>
 __global__ __launch_bounds__(256) void staged_opt_kernel(const OptArgs a) {
     constexpr bool SGD = MODE == 1;
+    constexpr bool EARLY_TABLES = NC <= 2;
     __shared__ int32_t perm_s[16][STAGE_SORT];
     const int t = threadIdx.x & 15;
+    const int lane0 = threadIdx.x & 48;  // the group's first lane inside its wavefront
     int32_t *const perm = perm_s[threadIdx.x >> 4];
-    const int64_t g0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4, ng = ((int64_t)gridDim.x * blockDim.x) >> 4;
-    const int64_t n_rows = a.sg_tot[0];
-    const int nchunk = a.ld >> 2;  // <= 64: up to 4 float4 chunks per lane
-    for (int64_t r = g0; r < n_rows; r += ng) {
-        const int4 e = a.sg_list[r];
-        const int row = e.x, n = e.z;
-        const float4 *const seg = (const float4 *)(a.stage + (int64_t)e.y * a.ld);
-        const float *const sb = a.stage_b + e.y;
-        const int32_t *const key = a.stage_key + e.y;
-        float4 g[4];
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    if (r >= a.sg_tot[0]) return;
+    const int nchunk = a.ld >> 2;  // <= 16 * NC
+    int cc[NC];    // this lane's chunks, clamped to the row
+    bool cok[NC];  // ... and whether the chunk exists
 #pragma unroll
-        for (int i = 0; i < 4; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        float gbias = 0.f;
-        auto add_row = [&](const float4 *src) {
+    for (int i = 0; i < NC; ++i) {
+        cok[i] = t + 16 * i < nchunk;
+        cc[i] = cok[i] ? t + 16 * i : nchunk - 1;
+    }
+    const float4 *const __restrict__ stage4 = (const float4 *)a.stage;
+    float4 *const E4 = (float4 *)a.E, *const mE4 = (float4 *)a.mE, *const vE4 = (float4 *)a.vE;
+    const int4 e = a.sg_list[r];
+    const int row = e.x, n = e.z;
+    const float4 *const seg = stage4 + (int64_t)e.y * nchunk;
+    const float *const sb = a.stage_b + e.y;
+    const int32_t *const key = a.stage_key + e.y;
+    const int64_t o4 = ((int64_t)row * a.ld) >> 2;
+    const int k0raw = key[t < n ? t : n - 1];
+    float4 var[NC], m[NC], v[NC];
+    float bvar = 0.f, bm = 0.f, bv = 0.f;  // (every lane of the group loads the row's bias words: one address, one request)
+    auto load_tables = [&]() {
+        if (MODE == 2) return;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = t + 16 * i;
-                if (c < nchunk) {
-                    const float4 x = src[c];
-                    g[i].x += x.x; g[i].y += x.y; g[i].z += x.z; g[i].w += x.w;
-                }
+        for (int i = 0; i < NC; ++i) {
+            var[i] = E4[o4 + cc[i]];
+            if (!SGD) { m[i] = mE4[o4 + cc[i]]; v[i] = vE4[o4 + cc[i]]; }
+        }
+        bvar = a.b[row];
+        if (!SGD) { bm = a.mb[row]; bv = a.vb[row]; }
+    };
+    if (EARLY_TABLES) load_tables();
+    float4 g[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float gbias = 0.f;
+    // stage rows at ranks o .. o + 3 in flight (all chunks, one wait), added in key order; pos(q) = segment position of rank q
+    auto sum_ranked = [&](auto pos) {
+        for (int o = 0; o < n; o += 4) {
+            float4 x[4][NC];
+            bool ok[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ok[j] = o + j < n;
+                const float4 *const s = seg + (int64_t)pos(ok[j] ? o + j : n - 1) * nchunk;
+#pragma unroll
+                for (int i = 0; i < NC; ++i) x[j][i] = s[cc[i]];
             }
-        };
-        if (n <= STAGE_SORT) {
-            if (n > 1) {  // rank of every key = number of smaller keys of the segment
-                int k[4], rk[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    k[i] = (t + 16 * i < n) ? key[t + 16 * i] : 0x7fffffff;
-                    rk[i] = 0;
-                }
+            for (int i = 0; i < NC; ++i) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (16 * j < n) {
-                        const int nl = min(n - 16 * j, 16);
-                        for (int l = 0; l < nl; ++l) {
-                            const int kk = __shfl(k[j], l, 16);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) rk[i] += kk < k[i];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (t + 16 * i < n) perm[rk[i]] = t + 16 * i;
-            } else if (t == 0) {
-                perm[0] = 0;
-            }
-            // the group's lanes sit in one wavefront: its LDS operations execute in program order
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // four stage rows in flight, added in key order
-            int o = 0;
-            for (; o + 4 <= n; o += 4) {
-                const float4 *s0 = seg + (int64_t)perm[o] * nchunk, *s1 = seg + (int64_t)perm[o + 1] * nchunk;
-                const float4 *s2 = seg + (int64_t)perm[o + 2] * nchunk, *s3 = seg + (int64_t)perm[o + 3] * nchunk;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int c = t + 16 * i;
-                    if (c < nchunk) {
-                        const float4 x0 = s0[c], x1 = s1[c], x2 = s2[c], x3 = s3[c];
-                        g[i].x += x0.x; g[i].y += x0.y; g[i].z += x0.z; g[i].w += x0.w;
-                        g[i].x += x1.x; g[i].y += x1.y; g[i].z += x1.z; g[i].w += x1.w;
-                        g[i].x += x2.x; g[i].y += x2.y; g[i].z += x2.z; g[i].w += x2.w;
-                        g[i].x += x3.x; g[i].y += x3.y; g[i].z += x3.z; g[i].w += x3.w;
-                    }
+                    g[i].x += ok[j] ? x[j][i].x : 0.f; g[i].y += ok[j] ? x[j][i].y : 0.f;
+                    g[i].z += ok[j] ? x[j][i].z : 0.f; g[i].w += ok[j] ? x[j][i].w : 0.f;
                 }
             }
-            for (; o < n; ++o) add_row(seg + (int64_t)perm[o] * nchunk);
-            for (int q = t; q < n; q += 16) gbias += sb[perm[q]];  // lane t: ranks t, t + 16, ... in order, then the butterfly
-            __builtin_amdgcn_wave_barrier();  // the next row's permutation is written behind these reads
+        }
+    };
+    if (n == 1) {
+        float4 x[NC];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) x[i] = seg[cc[i]];
+        const float sv = sb[0];
+        if (!EARLY_TABLES) load_tables();
+        __builtin_amdgcn_sched_barrier(0);  // (left alone, the scheduler puts the first add, and its wait, between these loads)
+#pragma unroll
+        for (int i = 0; i < NC; ++i) { g[i].x += x[i].x; g[i].y += x[i].y; g[i].z += x[i].z; g[i].w += x[i].w; }
+        if (t == 0) gbias += sv;
+    }
+    // (not an else: the wavefront runs the n = 1 groups first, with nothing of the other paths pending)
+    if (n > 1 && n <= 16) {  // one key per lane: rank = number of smaller keys, inverted by a push to lane `rank` of the group
+        const int k0 = t < n ? k0raw : 0x7fffffff;
+        int rk = 0;
+#pragma nounroll
+        for (int l = 0; l < n; ++l) rk += __shfl(k0, l, 16) < k0;
+        const int inv = __builtin_amdgcn_ds_permute((lane0 + (t < n ? rk : t)) << 2, t);  // lane q < n: position of rank q
+        const float sv = sb[t < n ? inv : 0];
+        sum_ranked([&](int q) { return __shfl(inv, q, 16); });
+        if (t < n) gbias += sv;
+    } else if (n > 16 && n <= STAGE_SORT) {  // rank of every key = number of smaller keys of the segment
+        int k[4], rk[4];
+        k[0] = k0raw;  // (t < 16 < n)
+        rk[0] = 0;
+#pragma unroll
+        for (int i = 1; i < 4; ++i) {
+            const int kr = key[t + 16 * i < n ? t + 16 * i : n - 1];
+            k[i] = (t + 16 * i < n) ? kr : 0x7fffffff;
+            rk[i] = 0;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (16 * j < n) {
+                const int nl = min(n - 16 * j, 16);
+#pragma nounroll
+                for (int l = 0; l < nl; ++l) {
+                    const int kk = __shfl(k[j], l, 16);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) rk[i] += kk < k[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (t + 16 * i < n) perm[rk[i]] = t + 16 * i;
+        // the group's lanes sit in one wavefront: its LDS operations execute in program order
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        sum_ranked([&](int q) { return perm[q]; });
+        for (int q = t; q < n; q += 16) gbias += sb[perm[q]];  // lane t: ranks t, t + 16, ... in order, then the butterfly
+    } else if (n > STAGE_SORT) {
+        int last = -1;  // keys are >= 0
+        for (int q = 0; q < n; ++q) {
+            int best = 0x7fffffff, besto = 0;
+            for (int o = t; o < n; o += 16) {
+                const int kk = key[o];
+                if (kk > last && kk < best) { best = kk; besto = o; }
+            }
+#pragma unroll
+            for (int w = 8; w >= 1; w >>= 1) {
+                const int ob = __shfl_xor(best, w, 16), oo = __shfl_xor(besto, w, 16);
+                if (ob < best) { best = ob; besto = oo; }
+            }
+            const float4 *const s = seg + (int64_t)besto * nchunk;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {  // (chunks behind the row's end add a copy of its last chunk: never stored)
+                const float4 x = s[cc[i]];
+                g[i].x += x.x; g[i].y += x.y; g[i].z += x.z; g[i].w += x.w;
+            }
+            if ((q & 15) == t) gbias += sb[besto];
+            last = best;
+        }
+    }
+    if (!EARLY_TABLES && n != 1) load_tables();
+    gbias += __shfl_xor(gbias, 8, 64);
+    gbias += __shfl_xor(gbias, 4, 64);
+    gbias += __shfl_xor(gbias, 2, 64);
+    gbias += __shfl_xor(gbias, 1, 64);
+    if (MODE == 2) {
+#pragma unroll
+        for (int i = 0; i < NC; ++i)
+            if (cok[i]) ((float4 *)a.gE)[o4 + cc[i]] = g[i];
+        if (t == 0) {
+            a.gb[row] = gbias;
+            a.touched[row] = 1;
+            a.sg_cnt[row] = 0;
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        if (SGD) {
+            var[i].x -= a.lr * g[i].x; var[i].y -= a.lr * g[i].y; var[i].z -= a.lr * g[i].z; var[i].w -= a.lr * g[i].w;
         } else {
-            int last = -1;  // keys are >= 0
-            for (int q = 0; q < n; ++q) {
-                int best = 0x7fffffff, besto = 0;
-                for (int o = t; o < n; o += 16) {
-                    const int kk = key[o];
-                    if (kk > last && kk < best) { best = kk; besto = o; }
-                }
-#pragma unroll
-                for (int m = 8; m >= 1; m >>= 1) {
-                    const int ob = __shfl_xor(best, m, 16), oo = __shfl_xor(besto, m, 16);
-                    if (ob < best) { best = ob; besto = oo; }
-                }
-                add_row(seg + (int64_t)besto * nchunk);
-                if ((q & 15) == t) gbias += sb[besto];
-                last = best;
-            }
+            adam_elem(var[i].x, m[i].x, v[i].x, g[i].x, a);
+            adam_elem(var[i].y, m[i].y, v[i].y, g[i].y, a);
+            adam_elem(var[i].z, m[i].z, v[i].z, g[i].z, a);
+            adam_elem(var[i].w, m[i].w, v[i].w, g[i].w, a);
         }
-        gbias += __shfl_xor(gbias, 8, 64);
-        gbias += __shfl_xor(gbias, 4, 64);
-        gbias += __shfl_xor(gbias, 2, 64);
-        gbias += __shfl_xor(gbias, 1, 64);
-        const int64_t o4 = ((int64_t)row * a.ld) >> 2;
-        if (MODE == 2) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = t + 16 * i;
-                if (c < nchunk) ((float4 *)a.gE)[o4 + c] = g[i];
+        if (cok[i]) {
+            if (!SGD) {
+                mE4[o4 + cc[i]] = m[i];
+                vE4[o4 + cc[i]] = v[i];
             }
-            if (t == 0) {
-                a.gb[row] = gbias;
-                a.touched[row] = 1;
-                a.sg_cnt[row] = 0;
-            }
-            continue;
+            if (nonfinite4(var[i])) *a.bad = 1ull;
+            E4[o4 + cc[i]] = var[i];
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = t + 16 * i;
-            if (c >= nchunk) continue;
-            float4 var = ((float4 *)a.E)[o4 + c];
-            if (SGD) {
-                var.x -= a.lr * g[i].x; var.y -= a.lr * g[i].y; var.z -= a.lr * g[i].z; var.w -= a.lr * g[i].w;
-            } else {
-                float4 m = ((float4 *)a.mE)[o4 + c], v = ((float4 *)a.vE)[o4 + c];
-                adam_elem(var.x, m.x, v.x, g[i].x, a);
-                adam_elem(var.y, m.y, v.y, g[i].y, a);
-                adam_elem(var.z, m.z, v.z, g[i].z, a);
-                adam_elem(var.w, m.w, v.w, g[i].w, a);
-                ((float4 *)a.mE)[o4 + c] = m;
-                ((float4 *)a.vE)[o4 + c] = v;
-            }
-            if (nonfinite4(var)) *a.bad = 1ull;
-            ((float4 *)a.E)[o4 + c] = var;
+    }
+    {
+        if (SGD) {
+            bvar -= a.lr * gbias;
+        } else {
+            adam_elem(bvar, bm, bv, gbias, a);
         }
         if (t == 0) {
-            float var = a.b[row];
-            if (SGD) {
-                var -= a.lr * gbias;
-            } else {
-                float m = a.mb[row], v = a.vb[row];
-                adam_elem(var, m, v, gbias, a);
-                a.mb[row] = m;
-                a.vb[row] = v;
+            if (!SGD) {
+                a.mb[row] = bm;
+                a.vb[row] = bv;
             }
-            if (!__builtin_isfinite(var)) *a.bad = 1ull;
-            a.b[row] = var;
+            if (!__builtin_isfinite(bvar)) *a.bad = 1ull;
+            a.b[row] = bvar;
             a.sg_cnt[row] = 0;
         }
     }
@@ -1372,6 +1431,22 @@ static int staged_reserve(gg_ctx *ctx, int64_t n_occ, int64_t n_stage) {
     return GG_OK;
 }
 
+// One group per list row.  The list's length is a device word; max_rows is what the host knows of it (the groups behind the
+// list's end leave at once).
+template <int MODE, int NC>
+static void launch_staged_opt_nc(gg_ctx *ctx, const OptArgs &o, int64_t max_rows) {
+    const int64_t nb = std::max<int64_t>(1, (max_rows * 16 + 255) / 256);
+    hipLaunchKernelGGL((staged_opt_kernel<MODE, NC>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, o);
+}
+
+// float4 chunks per lane of a 16-lane group: 1, 2 or 4 for ld <= 64, <= 128, <= 256 (staged_allowed: ld <= 256)
+template <int MODE>
+static void launch_staged_opt(gg_ctx *ctx, const OptArgs &o, int64_t max_rows) {
+    if (ctx->ld <= 64) launch_staged_opt_nc<MODE, 1>(ctx, o, max_rows);
+    else if (ctx->ld <= 128) launch_staged_opt_nc<MODE, 2>(ctx, o, max_rows);
+    else launch_staged_opt_nc<MODE, 4>(ctx, o, max_rows);
+}
+
 // ... and the update behind the gradient kernel: the small rows by the reducing optimizer, the hub rows through the flag
 // list and sparse_opt_kernel (apply_optimizer, which also advances the step count), the updated-row total for the timing
 static int staged_finish(gg_ctx *ctx, int which, int64_t n, int64_t n_occ, bool early_index = false) {
@@ -1382,13 +1457,11 @@ static int staged_finish(gg_ctx *ctx, int which, int64_t n, int64_t n_occ, bool 
     DevBuf &b_tot = early_index ? ctx->sgp_tot : ctx->sg_tot, &b_key = early_index ? ctx->sgp_key : ctx->sg_key;
     o.sg_cnt = b_cnt.as<int32_t>(); o.sg_list = b_list.as<int4>(); o.sg_tot = b_tot.as<int64_t>();
     o.stage = ctx->sg_rows.as<float>(); o.stage_b = ctx->sg_bias.as<float>(); o.stage_key = b_key.as<int32_t>();
-    int nb = cdiv((int64_t)std::min<int64_t>(n_occ, ctx->n_node) * 16, 256);
-    if (nb > 4096) nb = 4096;
-    if (nb < 1) nb = 1;
+    const int64_t max_rows = std::min<int64_t>(n_occ, ctx->n_node);
     const bool replicas = ctx->comm || ctx->fake_world > 1;  // the summed rows go through the accumulators and the exchange
-    if (replicas) hipLaunchKernelGGL(staged_opt_kernel<2>, dim3(nb), dim3(256), 0, ctx->stream, o);
-    else if (opt == GG_OPT_SGD) hipLaunchKernelGGL(staged_opt_kernel<1>, dim3(nb), dim3(256), 0, ctx->stream, o);
-    else hipLaunchKernelGGL(staged_opt_kernel<0>, dim3(nb), dim3(256), 0, ctx->stream, o);
+    if (replicas) launch_staged_opt<2>(ctx, o, max_rows);
+    else if (opt == GG_OPT_SGD) launch_staged_opt<1>(ctx, o, max_rows);
+    else launch_staged_opt<0>(ctx, o, max_rows);
     ctx->sg_active = true;  // the hub rows: flags -> list -> sparse_opt_kernel, which also resets their counts
     ctx->sg_cnt_active = o.sg_cnt;
     const int rc = apply_optimizer(ctx, which, n);
