@@ -45,6 +45,18 @@ struct ScopedBuf : DevBuf {
     ~ScopedBuf() { release(); }
 };
 
+// The staging index of one staged gradient pass (steps.hip): per table row the number of gradient rows staged for it (cnt) and the first stage row of its
+// segment (off), per pair end / path position its stage row (slot), the segments of the small rows (list), the source of each stage row = its place in the
+// sum order (key), the hub rows (hub) and three total words (tot: small rows, stage rows, hubs).  Plain buffers: released by gg_destroy, or by release().
+struct StageIndex {
+    DevBuf cnt, off, slot, list, tot, key, hub;
+    DevBuf scan;              // scan scratch of a build beside the main stream (one on the main stream uses the context's scan_tmp)
+    bool counts_zero = true;  // false from the moment a build is enqueued until staged_finish has applied and reset every counted row
+    int reserve(gg_ctx *ctx, int64_t n_node, int64_t n_occ, int64_t n_key, hipStream_t stream);  // steps.hip
+    void release() { for (DevBuf *b : {&cnt, &off, &slot, &list, &tot, &key, &hub, &scan}) b->release(); counts_zero = true; }
+    int32_t *slots() const { return slot.as<int32_t>(); }
+};
+
 // One embedding model (generator or discriminator): table, bias, Adam slots.
 struct Model {
     float *E = nullptr, *b = nullptr;      // [n_node * ld], [n_node]
@@ -253,26 +265,19 @@ struct gg_ctx {
     bool in_epoch_add = false;         // gg_prepare_* inside gg_epoch_add: no per-batch replica collective (the ranks' batch counts differ)
     int n_cus = 256;                       // compute units of the device (gg_create; hipGetDeviceProperties costs milliseconds)
     gg::DevBuf scan_tmp, step_u, step_v, step_x;
-    // staged generator gradient (steps.hip, run_path_step): per-row counts / segment offsets, per path node slot, row list,
-    // the stage itself (gradient rows + bias gradients of the small rows, segment by segment), two total words
-    gg::DevBuf sg_cnt, sg_off, sg_slot, sg_list, sg_rows, sg_bias, sg_tot, sg_key;  // sg_key: source of each stage row (sum order)
     bool g_pairs_filled = false;       // g_node1 / g_node2 hold the pairs of the resident G walks (prepare.hip, ensure_g_pairs)
-    bool sg_cnt_dirty = false;         // a staged pass counted rows and has not (yet) applied them
-    // The generator pass's staging INDEX (per-row counts, segment offsets, slots, small-row list, keys) depends on the G-mode walks
-    // only, so it is built on the side stream right behind them (enqueue_path_slots, steps.hip) -- beside the reward kernels
-    // of the main stream -- in buffers of its own (the discriminator pass uses sg_* at the same time); ev_slots_done orders the
-    // gradient kernel behind it.
-    gg::DevBuf sgp_cnt, sgp_off, sgp_slot, sgp_list, sgp_tot, sgp_key, sgp_scan, sgp_hub;  // sgp_hub: rows of the hubs of that index
-    gg::DevBuf sg_hub, hub_acc;        // hub rows of the pass's own index; their 64-bit fixed-point gradient sums (steps.hip, HubAcc)
-    int64_t hub_cap = 0;               // hubs hub_acc holds
+    // Staged gradient (steps.hip): large fused D passes and whole-walk G passes write their gradient rows to a stage (sg_rows, bias gradients in sg_bias), placed by
+    // a staging index, and staged_opt_kernel sums them in key order; the hubs' gradients are summed in 64-bit fixed point (hub_acc, HubAcc).  A pass builds sg_own on
+    // the main stream in front of its gradient kernel.  The generator pass's index depends on the G-mode walks only, so it is also built on the side stream right behind
+    // them (enqueue_path_slots), beside the reward kernels, into sg_early (the discriminator pass is using sg_own then); ev_slots_done orders the gradient kernel behind it.
+    gg::StageIndex sg_own, sg_early;
     hipEvent_t ev_slots_done = nullptr;
-    bool g_slots_ready = false;        // the index of the resident G-mode walks is enqueued / done
-    bool sgp_cnt_clean = false;        // sgp_cnt is all zero
-    int g_slots_unused = 0;            // early indexes in a row that no whole-walk generator pass consumed (2: stop building them)
-    int64_t g_slots_walks = 0;
-    int32_t g_slots_stride = 0;
-    int32_t *sg_cnt_active = nullptr;  // the count array of the staged pass that is applying its hub rows (sg_active)
-    bool sg_active = false;            // a staged G pass is applying its hub rows (apply_optimizer resets their counts)
+    bool g_slots_ready = false;        // sg_early holds the index of the resident G-mode walks (enqueued / done) ...
+    int64_t g_slots_walks = 0; int32_t g_slots_stride = 0;  // ... of this many walks at this path stride
+    int g_slots_unused = 0;           // early indexes in a row that no whole-walk generator pass consumed (2: stop building them)
+    const gg::StageIndex *sg_applying = nullptr;  // index of the staged pass that is applying its hub rows (apply_optimizer resets their counts)
+    gg::DevBuf sg_rows, sg_bias, hub_acc;
+    int64_t hub_cap = 0;               // hubs hub_acc holds
     int sg_threshold = 64;             // GG_STAGE_T: rows with more staged gradients than this are hubs (fixed-point sums); 0 = everything atomic
 
     // device-side counters of the walk launch in flight (zeroed at its start): [0]=hops [1]=nbr_reads [3]=error flag

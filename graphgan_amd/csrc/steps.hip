@@ -346,7 +346,7 @@ struct PathArgs {
 // <= T gradients get a contiguous segment of a stage buffer (device_segment_rows), the gradient kernel STORES each node's
 // row into its segment slot, and staged_opt_kernel sums a row's segment and applies the optimizer in the same pass: no
 // accumulator round trip.  The slot inside a segment is the rank the counting atomic returned, i.e. arrival order, which
-// differs from run to run; the sum does not: every stage row carries the path position it came from (sg_key) and the
+// differs from run to run; the sum does not: every stage row carries the path position it came from (the index's key) and the
 // reducing group adds its segment in ascending key order -- a deterministic sum for those rows.  Hub rows (> T gradients)
 // add 64-bit fixed-point sums (HubAcc: order independent), hub_finalize_kernel moves them into the fp32 accumulators, and
 // the flag -> list -> sparse_opt_kernel update applies them.
@@ -1312,6 +1312,10 @@ static OptArgs make_opt_args(gg_ctx *ctx, int which) {
     return o;
 }
 
+static void set_index_args(OptArgs &o, const StageIndex &ix) {
+    o.sg_cnt = ix.cnt.as<int32_t>(); o.sg_list = ix.list.as<int4>(); o.sg_tot = ix.tot.as<int64_t>(); o.stage_key = ix.key.as<int32_t>();
+}
+
 __global__ void set_count_kernel(int64_t *dst, int64_t v) { *dst = v; }
 
 // The generator's loss is a MEAN over the batch (generator.py:28): with replicas the batch of a step is the union
@@ -1380,39 +1384,74 @@ static HubAcc hub_args(gg_ctx *ctx, float scale) {
     return HubAcc{ctx->hub_acc.as<unsigned long long>(), ctx->hub_cap, scale};
 }
 
-// number the hubs of the index just built on `stream` (its totals word 2 counts them)
-static int hub_index(gg_ctx *ctx, const int32_t *cnt, int32_t *off, DevBuf &rows, int64_t *tot, hipStream_t stream) {
-    GG_HIP(ctx, rows.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
+// Buffers of an index over n_occ pair ends / path positions and at most n_key stage rows, for a build on `stream`.  The counts are zero between builds -- every
+// update resets the rows it applies -- unless the buffer is new or an earlier pass failed half way (counts_zero stays false): stale counts would mis-place stage rows.
+int StageIndex::reserve(gg_ctx *ctx, int64_t n_node, int64_t n_occ, int64_t n_key, hipStream_t stream) {
+    const size_t cnt_before = cnt.bytes;
+    GG_HIP(ctx, cnt.reserve(sizeof(int32_t) * (size_t)n_node));
+    if (cnt.bytes != cnt_before || !counts_zero) GG_HIP(ctx, hipMemsetAsync(cnt.p, 0, cnt.bytes, stream));
+    counts_zero = false;
+    for (DevBuf *b : {&off, &hub}) GG_HIP(ctx, b->reserve(sizeof(int32_t) * (size_t)n_node));
+    GG_HIP(ctx, list.reserve(sizeof(int4) * (size_t)n_node));
+    GG_HIP(ctx, slot.reserve(sizeof(int32_t) * (size_t)n_occ));
+    GG_HIP(ctx, key.reserve(sizeof(int32_t) * (size_t)n_key));
+    GG_HIP(ctx, tot.reserve(sizeof(int64_t) * 4));
+    return GG_OK;
+}
+
+// The middle of every build, behind the count kernel on `stream`: the segments of the small rows (offsets, list, totals 0 and 1)
+// and the numbers of the hubs (totals word 2 counts them).  A build beside the main stream's scans brings its own scan scratch.
+static int index_rows(gg_ctx *ctx, StageIndex &ix, hipStream_t stream) {
+    int32_t *cnt = ix.cnt.as<int32_t>(), *off = ix.off.as<int32_t>();
+    int64_t *tot = ix.tot.as<int64_t>();
+    const int rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ix.list.as<int4>(), tot, stream, stream == ctx->stream ? nullptr : &ix.scan);
+    if (rc != GG_OK) return rc;
     GG_HIP(ctx, hipMemsetAsync(tot + 2, 0, sizeof(int64_t), stream));
     hipLaunchKernelGGL(hub_index_kernel, dim3((unsigned)cdiv(ctx->n_node, 256)), dim3(256), 0, stream, cnt, (int64_t)ctx->n_node, ctx->sg_threshold, off,
-                       rows.as<int32_t>(), tot + 2);
+                       ix.hub.as<int32_t>(), tot + 2);
+    return GG_OK;  // (the caller asks for launch errors behind its slot kernel)
+}
+
+// The index of the 2 n pair ends of (u, v): slots of the v ends, then of the u ends (pair_occ_count_kernel).
+static int build_from_pairs(gg_ctx *ctx, StageIndex &ix, const int32_t *u, const int32_t *v, int32_t n, int ppg, hipStream_t stream) {
+    int32_t *cnt = ix.cnt.as<int32_t>(), *slot_v = ix.slots(), *slot_u = slot_v + n;
+    hipLaunchKernelGGL(pair_occ_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, u, v, n, ppg, cnt, slot_v, slot_u);
+    const int rc = index_rows(ctx, ix, stream);
+    if (rc != GG_OK) return rc;
+    hipLaunchKernelGGL(pair_occ_slot_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, u, v, n, cnt, ix.off.as<int32_t>(), ctx->sg_threshold, slot_v, slot_u,
+                       ix.key.as<int32_t>());
     GG_HIP(ctx, hipGetLastError());
     return GG_OK;
 }
 
-static void hub_finalize(gg_ctx *ctx, bool early_index, float scale, float *gE, float *gb) {
-    DevBuf &rows = early_index ? ctx->sgp_hub : ctx->sg_hub, &tot = early_index ? ctx->sgp_tot : ctx->sg_tot;
-    const int64_t n = ctx->hub_cap * (ctx->ld + 1);
-    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 2048));
-    hipLaunchKernelGGL(hub_finalize_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->hub_acc.as<unsigned long long>(), rows.as<int32_t>(),
-                       tot.as<int64_t>() + 2, ctx->hub_cap, ctx->ld, 1.0 / (double)scale, gE, gb);
+// The index of the n_walks x stride path positions of whole walks (path_count_kernel; `flag`: see there).
+static int build_from_paths(gg_ctx *ctx, StageIndex &ix, const int32_t *paths, const int32_t *len, int32_t stride, int64_t n_walks, const unsigned long long *flag, hipStream_t stream) {
+    const dim3 grid((unsigned)cdiv(n_walks * (int64_t)stride, 256));
+    int32_t *cnt = ix.cnt.as<int32_t>();
+    hipLaunchKernelGGL(path_count_kernel, grid, dim3(256), 0, stream, paths, len, stride, n_walks, cnt, ix.slots(), flag);
+    const int rc = index_rows(ctx, ix, stream);
+    if (rc != GG_OK) return rc;
+    hipLaunchKernelGGL(path_slot_kernel, grid, dim3(256), 0, stream, paths, len, stride, n_walks, cnt, ix.off.as<int32_t>(), ctx->sg_threshold, ix.slots(),
+                       ix.key.as<int32_t>(), flag);
+    GG_HIP(ctx, hipGetLastError());
+    return GG_OK;
 }
 
+// the hubs' fixed-point sums -> the gradient accumulators (and zero again)
+static void hub_finalize(gg_ctx *ctx, const StageIndex &ix, float scale) {
+    const int64_t n = ctx->hub_cap * (ctx->ld + 1);
+    const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 256), 2048));
+    hipLaunchKernelGGL(hub_finalize_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->hub_acc.as<unsigned long long>(), ix.hub.as<int32_t>(),
+                       ix.tot.as<int64_t>() + 2, ctx->hub_cap, ctx->ld, 1.0 / (double)scale, ctx->gradE, ctx->gradb);
+}
+
+// The pass's own index (n_key = n_stage) and what is no part of an index: the stage and the hub sums.  1 = they do not fit.
 static int staged_reserve(gg_ctx *ctx, int64_t n_occ, int64_t n_stage) {
     if (n_stage * (int64_t)(ctx->ld + 2) * 4 > stage_bytes_cap()) return 1;
-    const size_t cnt_before = ctx->sg_cnt.bytes;
-    GG_HIP(ctx, ctx->sg_cnt.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
-    // the counts are zero between passes -- every update resets the rows it applies -- unless the buffer is new or an earlier
-    // staged pass failed half way (sg_cnt_dirty stays set): then they are cleared here, stale counts would mis-place stage rows
-    const bool was_dirty = ctx->sg_cnt_dirty;  // (a pass that failed half way may also have left hub sums behind)
-    if (ctx->sg_cnt.bytes != cnt_before || ctx->sg_cnt_dirty) GG_HIP(ctx, hipMemsetAsync(ctx->sg_cnt.p, 0, ctx->sg_cnt.bytes, ctx->stream));
-    ctx->sg_cnt_dirty = true;
-    GG_HIP(ctx, ctx->sg_off.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
-    GG_HIP(ctx, ctx->sg_list.reserve(sizeof(int4) * (size_t)ctx->n_node));
-    GG_HIP(ctx, ctx->sg_slot.reserve(sizeof(int32_t) * (size_t)n_occ));
+    const bool was_dirty = !ctx->sg_own.counts_zero;  // (a pass that failed half way may also have left hub sums behind)
+    const int rc = ctx->sg_own.reserve(ctx, ctx->n_node, n_occ, n_stage, ctx->stream);
+    if (rc != GG_OK) return rc;
     GG_HIP(ctx, ctx->sg_bias.reserve(sizeof(float) * (size_t)n_stage));
-    GG_HIP(ctx, ctx->sg_key.reserve(sizeof(int32_t) * (size_t)n_stage));
-    GG_HIP(ctx, ctx->sg_tot.reserve(sizeof(int64_t) * 4));
     {  // a hub has more than T of the n_occ gradients; the sums stay zero between passes (hub_finalize_kernel clears them)
         const int64_t cap = std::min<int64_t>(ctx->n_node, n_occ / ((int64_t)ctx->sg_threshold + 1) + 1);
         const size_t before = ctx->hub_acc.bytes;
@@ -1432,53 +1471,59 @@ static int staged_reserve(gg_ctx *ctx, int64_t n_occ, int64_t n_stage) {
 }
 
 // One group per list row.  The list's length is a device word; max_rows is what the host knows of it (the groups behind the
-// list's end leave at once).
-template <int MODE, int NC>
-static void launch_staged_opt_nc(gg_ctx *ctx, const OptArgs &o, int64_t max_rows) {
-    const int64_t nb = std::max<int64_t>(1, (max_rows * 16 + 255) / 256);
-    hipLaunchKernelGGL((staged_opt_kernel<MODE, NC>), dim3((unsigned)nb), dim3(256), 0, ctx->stream, o);
-}
-
-// float4 chunks per lane of a 16-lane group: 1, 2 or 4 for ld <= 64, <= 128, <= 256 (staged_allowed: ld <= 256)
+// list's end leave at once).  float4 chunks per lane of a 16-lane group: 1, 2 or 4 for ld <= 64, <= 128, <= 256 (staged_allowed: ld <= 256)
 template <int MODE>
 static void launch_staged_opt(gg_ctx *ctx, const OptArgs &o, int64_t max_rows) {
-    if (ctx->ld <= 64) launch_staged_opt_nc<MODE, 1>(ctx, o, max_rows);
-    else if (ctx->ld <= 128) launch_staged_opt_nc<MODE, 2>(ctx, o, max_rows);
-    else launch_staged_opt_nc<MODE, 4>(ctx, o, max_rows);
+    const dim3 g((unsigned)std::max<int64_t>(1, (max_rows * 16 + 255) / 256)), b(256);
+    if (ctx->ld <= 64) hipLaunchKernelGGL((staged_opt_kernel<MODE, 1>), g, b, 0, ctx->stream, o);
+    else if (ctx->ld <= 128) hipLaunchKernelGGL((staged_opt_kernel<MODE, 2>), g, b, 0, ctx->stream, o);
+    else hipLaunchKernelGGL((staged_opt_kernel<MODE, 4>), g, b, 0, ctx->stream, o);
 }
 
-// ... and the update behind the gradient kernel: the small rows by the reducing optimizer, the hub rows through the flag
-// list and sparse_opt_kernel (apply_optimizer, which also advances the step count), the updated-row total for the timing
-static int staged_finish(gg_ctx *ctx, int which, int64_t n, int64_t n_occ, bool early_index = false) {
-    const int opt = ctx->cfg.optimizer;
+// ... and what follows the gradient kernel: the hubs' sums, then the update -- the small rows by the reducing optimizer, the hub rows through
+// the flag list and sparse_opt_kernel (apply_optimizer, which also advances the step count) -- and the updated-row total for the timing
+static int staged_finish(gg_ctx *ctx, int which, int64_t n, int64_t n_occ, StageIndex &ix, float scale) {
+    hub_finalize(ctx, ix, scale);
+    if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | optimizer
     OptArgs o = make_opt_args(ctx, which);  // before apply_optimizer advances the step count and the beta powers
-    // the staging index: the pass's own (sg_*), or the one built on the side stream behind the G-mode walks (sgp_*)
-    DevBuf &b_cnt = early_index ? ctx->sgp_cnt : ctx->sg_cnt, &b_list = early_index ? ctx->sgp_list : ctx->sg_list;
-    DevBuf &b_tot = early_index ? ctx->sgp_tot : ctx->sg_tot, &b_key = early_index ? ctx->sgp_key : ctx->sg_key;
-    o.sg_cnt = b_cnt.as<int32_t>(); o.sg_list = b_list.as<int4>(); o.sg_tot = b_tot.as<int64_t>();
-    o.stage = ctx->sg_rows.as<float>(); o.stage_b = ctx->sg_bias.as<float>(); o.stage_key = b_key.as<int32_t>();
+    set_index_args(o, ix);
+    o.stage = ctx->sg_rows.as<float>(); o.stage_b = ctx->sg_bias.as<float>();
     const int64_t max_rows = std::min<int64_t>(n_occ, ctx->n_node);
     const bool replicas = ctx->comm || ctx->fake_world > 1;  // the summed rows go through the accumulators and the exchange
     if (replicas) launch_staged_opt<2>(ctx, o, max_rows);
-    else if (opt == GG_OPT_SGD) launch_staged_opt<1>(ctx, o, max_rows);
+    else if (ctx->cfg.optimizer == GG_OPT_SGD) launch_staged_opt<1>(ctx, o, max_rows);
     else launch_staged_opt<0>(ctx, o, max_rows);
-    ctx->sg_active = true;  // the hub rows: flags -> list -> sparse_opt_kernel, which also resets their counts
-    ctx->sg_cnt_active = o.sg_cnt;
+    ctx->sg_applying = &ix;  // the hub rows: flags -> list -> sparse_opt_kernel, which also resets their counts
     const int rc = apply_optimizer(ctx, which, n);
-    ctx->sg_active = false;
+    ctx->sg_applying = nullptr;
     if (rc != GG_OK) return rc;
     // rows this pass updated (read back by the timing harvest): hub rows + small rows
     if (!replicas)
-        hipLaunchKernelGGL(add_word_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->touched_ptr.as<int64_t>() + ctx->n_node, b_tot.as<int64_t>());
+        hipLaunchKernelGGL(add_word_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->touched_ptr.as<int64_t>() + ctx->n_node, o.sg_tot);
     GG_HIP(ctx, hipGetLastError());
-    if (early_index) ctx->sgp_cnt_clean = true;  // every counted row was applied and reset
-    else ctx->sg_cnt_dirty = false;
+    ix.counts_zero = true;  // every counted row was applied and reset
     return GG_OK;
 }
 
 // (the reducing kernel holds a row's sum in 4 float4 per lane: ld <= 256; wider tables keep the atomic kernels)
 static bool staged_allowed(const gg_ctx *ctx) {
     return ctx->sg_threshold > 0 && ctx->ld <= 256 && ctx->cfg.optimizer != GG_OPT_ADAM_DENSE && !getenv("GG_NO_STAGED_GRAD");
+}
+
+// Gradient kernel of a pair batch: 16 pairs per group when STAGED (which implies ppg = 16, ld <= 256) and for large batches on the atomic path (replicas, dense Adam; no wide rows)
+template <bool STAGED>
+static void launch_pair_grad(gg_ctx *ctx, const StepArgs &s, int blocks, int nf) {
+    const dim3 g(blocks), b(256);
+    if (STAGED || (s.ppg == PAIRS_PER_GROUP && nf <= 16 && !getenv("GG_OLD_PAIR_GRAD"))) {
+        if (nf <= 4) hipLaunchKernelGGL((pair_grad16_kernel<4, STAGED>), g, b, 0, ctx->stream, s);
+        else if (nf <= 8) hipLaunchKernelGGL((pair_grad16_kernel<8, STAGED>), g, b, 0, ctx->stream, s);
+        else hipLaunchKernelGGL((pair_grad16_kernel<16, STAGED>), g, b, 0, ctx->stream, s);
+    } else if constexpr (!STAGED) {
+        if (nf <= 4) hipLaunchKernelGGL((pair_grad_kernel<4, false>), g, b, 0, ctx->stream, s);
+        else if (nf <= 8) hipLaunchKernelGGL((pair_grad_kernel<8, false>), g, b, 0, ctx->stream, s);
+        else if (nf <= 16) hipLaunchKernelGGL((pair_grad_kernel<16, false>), g, b, 0, ctx->stream, s);
+        else hipLaunchKernelGGL((pair_grad_kernel<32, false>), g, b, 0, ctx->stream, s);
+    }
 }
 
 // One optimizer step of model `which` on n device-resident rows.
@@ -1553,44 +1598,21 @@ int run_step(gg_ctx *ctx, int which, const int32_t *d_u, const int32_t *d_v, con
     const int blocks = cdiv((int64_t)groups * 16, 256);
     const int nf = (ctx->ld + 15) / 16;
     // large fused batches on one replica: staged gradient rows + reducing optimizer instead of fp32 atomics (see path_count_kernel)
-    bool staged = n >= 16384 && n < (1 << 30) && staged_allowed(ctx);
-    if (staged) {
-        int rc = staged_reserve(ctx, 2 * (int64_t)n, 2 * (int64_t)n);
-        if (rc < 0) return rc;
-        if (rc == 1) staged = false;  // the stage does not fit: atomics
-    }
-    if (staged) {
-        int rc;
-        int32_t *cnt = ctx->sg_cnt.as<int32_t>(), *off = ctx->sg_off.as<int32_t>(), *slot_v = ctx->sg_slot.as<int32_t>(), *slot_u = slot_v + n;
-        hipLaunchKernelGGL(pair_occ_count_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_u, d_v, n, s.ppg, cnt, slot_v, slot_u);
-        rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sg_list.as<int4>(), ctx->sg_tot.as<int64_t>());
+    const int fit = n >= 16384 && n < (1 << 30) && staged_allowed(ctx) ? staged_reserve(ctx, 2 * (int64_t)n, 2 * (int64_t)n) : 1;
+    if (fit < 0) return fit;
+    if (fit == GG_OK) {  // (1: not asked for, or the stage does not fit: atomics)
+        StageIndex &ix = ctx->sg_own;
+        const int rc = build_from_pairs(ctx, ix, d_u, d_v, n, s.ppg, ctx->stream);
         if (rc != GG_OK) return rc;
-        rc = hub_index(ctx, cnt, off, ctx->sg_hub, ctx->sg_tot.as<int64_t>(), ctx->stream);
-        if (rc != GG_OK) return rc;
-        hipLaunchKernelGGL(pair_occ_slot_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_u, d_v, n, cnt, off, ctx->sg_threshold, slot_v, slot_u,
-                           ctx->sg_key.as<int32_t>());
-        s.slot_v = slot_v; s.slot_u = slot_u;
+        s.slot_v = ix.slots(); s.slot_u = s.slot_v + n;
         s.stage = ctx->sg_rows.as<float>(); s.stage_b = ctx->sg_bias.as<float>();
         const float scale = hub_scale(!s.is_d, n);
         s.hub = hub_args(ctx, scale);
-        // (staged implies ppg = 16 and ld <= 256)
-        if (nf <= 4) hipLaunchKernelGGL((pair_grad16_kernel<4, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-        else if (nf <= 8) hipLaunchKernelGGL((pair_grad16_kernel<8, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-        else hipLaunchKernelGGL((pair_grad16_kernel<16, true>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-        hub_finalize(ctx, false, scale, s.gE, s.gb);
-        if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | optimizer
-        return staged_finish(ctx, which, n, 2 * (int64_t)n);
+        launch_pair_grad<true>(ctx, s, blocks, nf);
+        return staged_finish(ctx, which, n, 2 * (int64_t)n, ix, scale);
     }
-    if (s.ppg == PAIRS_PER_GROUP && nf <= 16 && !getenv("GG_OLD_PAIR_GRAD")) {  // large fused batch on the atomic path (replicas, dense Adam, wide rows excluded)
-        if (nf <= 4) hipLaunchKernelGGL((pair_grad16_kernel<4, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-        else if (nf <= 8) hipLaunchKernelGGL((pair_grad16_kernel<8, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-        else hipLaunchKernelGGL((pair_grad16_kernel<16, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-    } else if (nf <= 4) hipLaunchKernelGGL((pair_grad_kernel<4, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-    else if (nf <= 8) hipLaunchKernelGGL((pair_grad_kernel<8, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-    else if (nf <= 16) hipLaunchKernelGGL((pair_grad_kernel<16, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
-    else hipLaunchKernelGGL((pair_grad_kernel<32, false>), dim3(blocks), dim3(256), 0, ctx->stream, s);
+    launch_pair_grad<false>(ctx, s, blocks, nf);
     if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | exchange + optimizer
-
     return apply_optimizer(ctx, which, n);
 }
 
@@ -1633,91 +1655,58 @@ int run_path_step(gg_ctx *ctx) {
     const int blocks = cdiv(p.n_walks * 16, 256);
     const int nf = (ctx->ld + 15) / 16;
     const int64_t n_pos = p.n_walks * (int64_t)p.stride;
-    bool staged = staged_allowed(ctx) && n_pos < (1ll << 31);
     // staged rows = path nodes of the walks that have pairs: a walk of L >= 2 nodes has 4L - 6 (window 2; L = 2: 2) resp.
     // 2L - 2 (window 1) pairs, so sum L <= (pairs + 6 walks) / 4 resp. (pairs + 2 walks) / 2 -- from host-side numbers, and
     // several times smaller than the walks x stride slot array
     const int64_t n_stage = std::min<int64_t>(n_pos, p.window >= 2 ? (n + 6 * p.n_walks) / 4 + 1 : (n + 2 * p.n_walks) / 2 + 1);
-    if (staged) {
-        const int rc = staged_reserve(ctx, n_pos, n_stage);
-        if (rc < 0) return rc;
-        if (rc == 1) staged = false;
-    }
-    if (!staged) {
+    const int fit = staged_allowed(ctx) && n_pos < (1ll << 31) ? staged_reserve(ctx, n_pos, n_stage) : 1;
+    if (fit < 0) return fit;
+    if (fit != GG_OK) {  // not asked for, or the stage does not fit: atomics
         launch_path_grad<false>(ctx, p, blocks, nf);
         if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | exchange + optimizer
         return apply_optimizer(ctx, 0, n);
     }
     // ---- staged gradient (see path_count_kernel)
-    int rc;
-    int32_t *cnt = ctx->sg_cnt.as<int32_t>(), *off = ctx->sg_off.as<int32_t>(), *slot = ctx->sg_slot.as<int32_t>();
-    const dim3 pgrid((unsigned)cdiv(n_pos, 256));
     // the index of these walks may already be on its way (side stream, behind the walks: enqueue_path_slots)
     const bool early = ctx->g_slots_ready && ctx->g_slots_walks == p.n_walks && ctx->g_slots_stride == p.stride;
     ctx->g_slots_ready = false;
     ctx->g_slots_unused = 0;  // this caller takes whole-walk passes: keep (or resume) building the index early
+    StageIndex &ix = early ? ctx->sg_early : ctx->sg_own;
     if (early) {
-        ctx->sg_cnt_dirty = false;  // (staged_reserve left the pass's own count array clean, and this pass does not use it)
+        ctx->sg_own.counts_zero = true;  // (staged_reserve left the pass's own counts zero, and this pass does not build on them)
         GG_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slots_done, 0));
-        slot = ctx->sgp_slot.as<int32_t>();
     } else {
-        hipLaunchKernelGGL(path_count_kernel, pgrid, dim3(256), 0, ctx->stream, p.paths, p.path_len, p.stride, p.n_walks, cnt, slot, (const unsigned long long *)nullptr);
-        rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sg_list.as<int4>(), ctx->sg_tot.as<int64_t>());
+        const int rc = build_from_paths(ctx, ix, p.paths, p.path_len, p.stride, p.n_walks, nullptr, ctx->stream);
         if (rc != GG_OK) return rc;
-        rc = hub_index(ctx, cnt, off, ctx->sg_hub, ctx->sg_tot.as<int64_t>(), ctx->stream);
-        if (rc != GG_OK) return rc;
-        hipLaunchKernelGGL(path_slot_kernel, pgrid, dim3(256), 0, ctx->stream, p.paths, p.path_len, p.stride, p.n_walks, cnt, off, ctx->sg_threshold, slot,
-                           ctx->sg_key.as<int32_t>(), (const unsigned long long *)nullptr);
     }
-    p.slot = slot;
+    p.slot = ix.slots();
     p.stage = ctx->sg_rows.as<float>();
     p.stage_b = ctx->sg_bias.as<float>();
     const float scale = hub_scale(true, n);
     p.hub = hub_args(ctx, scale);
     launch_path_grad<true>(ctx, p, blocks, nf);
-    hub_finalize(ctx, early, scale, p.gE, p.gb);
-    if (ctx->tm_cur >= 0) GG_HIP(ctx, hipEventRecord(ctx->tm_ev[ctx->tm_cur][1], ctx->stream));  // gradient | optimizer
-    return staged_finish(ctx, 0, n, n_pos, early);
+    return staged_finish(ctx, 0, n, n_pos, ix, scale);
 }
 
 // The staging index of the G-mode walks that were just enqueued on the side stream, right behind them on that stream: per-row
 // counts of the path nodes, segments of the small rows, the nodes' slots and keys (what run_path_step used to launch in front
 // of its gradient kernel: ~0.12 ms of the step's critical path at the bench batch; here it runs beside the reward kernels).
-// The index has buffers of its own: the discriminator pass is using sg_* on the main stream at this very time.
+// The index has buffers of its own: the discriminator pass is using sg_own on the main stream at this very time.
 int enqueue_path_slots(gg_ctx *ctx) {
     ctx->g_slots_ready = false;
     if (ctx->walk_stream == ctx->stream || ctx->in_epoch_add || getenv("GG_NO_EARLY_SLOTS")) return GG_OK;
     const int64_t n_walks = ctx->w_total, n_pos = n_walks * (int64_t)ctx->w_stride;
     if (!staged_allowed(ctx) || ctx->cfg.window_size > 2 || n_walks == 0 || n_pos >= (1ll << 31)) return GG_OK;
     if (ctx->g_slots_unused >= 2) {  // the caller runs minibatch steps (run_step): the index would be built and dropped per prepare_g
-        if (ctx->sgp_slot.p) {       // (hipFree waits for the device: once, when the schedule is recognised)
-            for (DevBuf *b : {&ctx->sgp_cnt, &ctx->sgp_off, &ctx->sgp_slot, &ctx->sgp_list, &ctx->sgp_key, &ctx->sgp_scan, &ctx->sgp_hub}) b->release();
-            ctx->sgp_cnt_clean = false;
-        }
+        if (ctx->sg_early.slot.p) ctx->sg_early.release();  // (hipFree waits for the device: once, when the schedule is recognised)
         return GG_OK;
     }
     hipStream_t st = ctx->walk_stream;
-    const size_t cnt_before = ctx->sgp_cnt.bytes;
-    GG_HIP(ctx, ctx->sgp_cnt.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
-    if (ctx->sgp_cnt.bytes != cnt_before || !ctx->sgp_cnt_clean) GG_HIP(ctx, hipMemsetAsync(ctx->sgp_cnt.p, 0, ctx->sgp_cnt.bytes, st));
-    ctx->sgp_cnt_clean = false;
-    GG_HIP(ctx, ctx->sgp_off.reserve(sizeof(int32_t) * (size_t)ctx->n_node));
-    GG_HIP(ctx, ctx->sgp_list.reserve(sizeof(int4) * (size_t)ctx->n_node));
-    GG_HIP(ctx, ctx->sgp_slot.reserve(sizeof(int32_t) * (size_t)n_pos));
-    GG_HIP(ctx, ctx->sgp_key.reserve(sizeof(int32_t) * (size_t)n_pos));  // (staged rows <= path positions)
-    GG_HIP(ctx, ctx->sgp_tot.reserve(sizeof(int64_t) * 4));
+    int rc = ctx->sg_early.reserve(ctx, ctx->n_node, n_pos, n_pos, st);  // (staged rows <= path positions)
+    if (rc != GG_OK) return rc;
     if (!ctx->ev_slots_done) GG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_slots_done, hipEventDisableTiming));
-    const unsigned long long *flag = ctx->dev_ctr + 3;
-    const dim3 pgrid((unsigned)cdiv(n_pos, 256));
-    int32_t *cnt = ctx->sgp_cnt.as<int32_t>(), *off = ctx->sgp_off.as<int32_t>(), *slot = ctx->sgp_slot.as<int32_t>();
-    hipLaunchKernelGGL(path_count_kernel, pgrid, dim3(256), 0, st, ctx->w_paths.as<int32_t>(), ctx->w_len.as<int32_t>(), ctx->w_stride, n_walks, cnt, slot, flag);
-    int rc = device_segment_rows(ctx, cnt, ctx->n_node, ctx->sg_threshold, off, ctx->sgp_list.as<int4>(), ctx->sgp_tot.as<int64_t>(), st, &ctx->sgp_scan);
+    rc = build_from_paths(ctx, ctx->sg_early, ctx->w_paths.as<int32_t>(), ctx->w_len.as<int32_t>(), ctx->w_stride, n_walks, ctx->dev_ctr + 3, st);
     if (rc != GG_OK) return rc;
-    rc = hub_index(ctx, cnt, off, ctx->sgp_hub, ctx->sgp_tot.as<int64_t>(), st);
-    if (rc != GG_OK) return rc;
-    hipLaunchKernelGGL(path_slot_kernel, pgrid, dim3(256), 0, st, ctx->w_paths.as<int32_t>(), ctx->w_len.as<int32_t>(), ctx->w_stride, n_walks, cnt, off,
-                       ctx->sg_threshold, slot, ctx->sgp_key.as<int32_t>(), flag);
-    GG_HIP(ctx, hipGetLastError());
     GG_HIP(ctx, hipEventRecord(ctx->ev_slots_done, st));
     ctx->g_slots_ready = true;
     ctx->g_slots_walks = n_walks;
@@ -2078,7 +2067,7 @@ int apply_optimizer(gg_ctx *ctx, int which, int64_t n) {
     if (rc != GG_OK) return rc;
 
     OptArgs o = make_opt_args(ctx, which);
-    if (ctx->sg_active) o.sg_cnt = ctx->sg_cnt_active;  // hub rows of a staged pass: the row's count is reset with its flag
+    if (ctx->sg_applying) o.sg_cnt = ctx->sg_applying->cnt.as<int32_t>();  // hub rows of a staged pass: the row's count is reset with its flag
     if (opt == GG_OPT_ADAM_DENSE) {
         int64_t nb = (o.nE / 4 + 255) / 256;
         if (nb > 2048) nb = 2048;
