@@ -131,6 +131,7 @@ SIGNATURES = {
     "gg_edge_classifier_predict": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _i64, _P, _P, _P]),
     "gg_kmeans_step": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gg_kmeans_fit": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_silhouette": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _i64, ctypes.c_int, _P, _i64, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

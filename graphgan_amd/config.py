@@ -101,6 +101,13 @@ engine_node_clustering = False
 engine_cluster_k = 0            # clusters; 0 = the number of distinct labels
 engine_cluster_n_init = 4       # k-means++ restarts; the lowest final inertia is kept
 engine_cluster_max_iters = 100  # Lloyd sweeps of a restart at most
+# silhouette of those partitions (evaluation/node_silhouette.py): with engine_cluster_silhouette = True (needs engine_node_clustering)
+# evaluation() appends, after the two *_cluster lines and before gen_nll, "gen_sil:sil= label_sil= k= n= rows= precision=" and
+# "dis_sil:..." -- the exact mean silhouette over ALL pairs (gg_silhouette) of the k-means partition the *_cluster line reports and of
+# the labels taken as the partition.  No labels are needed to COMPUTE a silhouette (Engine.silhouette); this evaluator reports both.
+engine_cluster_silhouette = False
+engine_sil_precision = "fp32"   # distances from exact "fp32" scores or "bf16" (the silhouette of the bf16-rounded table)
+engine_sil_max_rows = 0         # 0 = every row; else a sample of that many rows (RandomState([engine_seed, 0x5349])) against all columns
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

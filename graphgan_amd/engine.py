@@ -931,6 +931,56 @@ class Engine:
         step = lambda chosen: self.kmeans_step(nodes_a, centroid_nodes=nodes_a[chosen], which=which, sums=False)["dist2"]  # noqa: E731
         return kmeans_pp_positions(len(nodes_a), int(k), seed, step)
 
+    # ------------------------------------------------------------------ silhouette of a partition (gg_silhouette)
+    def silhouette(self, nodes, assign, k=None, rows=None, which=0, precision="fp32"):
+        """The exact silhouette of the partition ``assign`` of the rows ``nodes`` of table ``which`` over ALL pairs (gg_silhouette;
+        Euclidean distance, the definition in include/graphgan_hip.h), streamed on the device: nothing of size m x m exists.
+        ``nodes``: 1-d integers, m >= 2 DISTINCT node ids; ``assign``: 1-d integers [m] in [0, k) with at least two non-empty
+        clusters; ``k``: integer in [2, 128], None = max(assign) + 1; ``rows``: None (every position) or 1-d integers, positions
+        into ``nodes`` (free to repeat), each evaluated against all m columns with the full call's bits; precision "fp32" or
+        "bf16" (the silhouette of the bf16-rounded table).  Returns dict(sil fp32, a fp32, b fp32, nearest int32 -- each
+        [len(rows) or m] --, mean float, ms)."""
+        fn = "silhouette"
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("%s: precision must be 'fp32' or 'bf16', got %r" % (fn, precision))
+        if which not in (0, 1):
+            raise ValueError("%s: which must be 0 (generator) or 1 (discriminator), got %r" % (fn, which))
+        nodes_a, assign_a = np.asarray(nodes), np.asarray(assign)
+        for name, arr in (("nodes", nodes_a), ("assign", assign_a)):
+            if arr.ndim != 1 or not np.issubdtype(arr.dtype, np.integer) or arr.dtype == np.bool_:
+                raise ValueError("%s: %s must be a 1-d array of integers" % (fn, name))
+        m = len(nodes_a)
+        if m < 2:
+            raise ValueError("%s: m = %d outside [2, 2^31 - 1]" % (fn, m))
+        if len(assign_a) != m:
+            raise ValueError("%s: nodes and assign must have the same length, got %d and %d" % (fn, m, len(assign_a)))
+        if k is None:
+            k = int(assign_a.max()) + 1
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 128:
+            raise ValueError("%s: k must be an integer in [2, 128], got %r" % (fn, k))
+        k = int(k)
+        if int(nodes_a.min()) < 0 or int(nodes_a.max()) >= self.n_node:
+            raise ValueError("%s: node id outside [0, %d)" % (fn, self.n_node))
+        if int(assign_a.min()) < 0 or int(assign_a.max()) >= k:
+            raise ValueError("%s: assign outside [0, k = %d)" % (fn, k))
+        rows_a = None
+        if rows is not None:
+            rows_a = np.asarray(rows)
+            if rows_a.ndim != 1 or rows_a.size == 0 or not np.issubdtype(rows_a.dtype, np.integer) or rows_a.dtype == np.bool_:
+                raise ValueError("%s: rows must be None or a non-empty 1-d array of integers" % fn)
+            if int(rows_a.min()) < 0 or int(rows_a.max()) >= m:
+                raise ValueError("%s: rows outside [0, m = %d)" % (fn, m))
+            rows_a = np.ascontiguousarray(rows_a, dtype=np.int64)
+        n_out = m if rows_a is None else len(rows_a)
+        nodes_a, assign_a = _i32(nodes_a), _i32(assign_a)
+        sil, a, b = (np.empty(n_out, dtype=np.float32) for _ in range(3))
+        nearest = np.empty(n_out, dtype=np.int32)
+        mean = np.zeros(1, dtype=np.float64)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_silhouette(self._ctx, which, _ptr(nodes_a), _ptr(assign_a), m, k, _ptr(rows_a), n_out if rows_a is not None else 0,
+                                   {"fp32": 0, "bf16": 1}[precision], _ptr(sil), _ptr(a), _ptr(b), _ptr(nearest), _ptr(mean), ctypes.byref(ms)))
+        return dict(sil=sil, a=a, b=b, nearest=nearest, mean=float(mean[0]), ms=ms.value)
+
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""
         out = np.zeros((self.n_node, self.n_emb), dtype=np.float32)

@@ -156,6 +156,8 @@ class NodeClusterEval(object):
         if len(nodes) < k:
             raise ValueError("node clustering: %d labelled nodes are fewer than k = %d clusters" % (len(nodes), k))
         res = self.fit(nodes, k)
+        # the kept fit, for evaluators that judge the same partition (node_silhouette.py): not part of the returned scores
+        self.last_partition = dict(nodes=nodes, classes=classes, assign=np.asarray(res["assign"]), k=int(k), n_labels=len(values))
         scores = cluster_metrics(classes, res["assign"])
         return dict(scores, inertia=float(res["inertia"][-1]), k=int(k), n=int(len(nodes)), iters=int(res["iters"]),
                     empty=int((np.asarray(res["counts"]) == 0).sum()))

@@ -49,6 +49,7 @@ from graphgan_amd.evaluation import generator_likelihood as gl  # noqa: E402
 from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
 from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
+from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -83,7 +84,10 @@ def _check_link_rank(cfg):
 
 
 def _check_node_clustering(cfg):
-    """the clustering lines need the labels file, under any app (checked before anything is computed)"""
+    """the clustering lines need the labels file, under any app (checked before anything is computed); the silhouette lines
+    judge the clustering lines' partition"""
+    if _cfg(cfg, "engine_cluster_silhouette", False) and not _cfg(cfg, "engine_node_clustering", False):
+        raise ValueError("engine_cluster_silhouette needs engine_node_clustering = True: it scores the k-means partition of the *_cluster lines")
     if not _cfg(cfg, "engine_node_clustering", False):
         return
     path = getattr(cfg, "labels_filename", None)
@@ -534,11 +538,23 @@ class GraphGAN(object):
             # k-means on the frozen rows of all labelled nodes (gg_kmeans_step / gg_kmeans_fit), scored against the labels: one line
             # per mode, "gen_cluster:NMI=<n> ARI=<a> purity=<p> inertia=<i> k=<k> n=<n> iters=<t> empty=<e>" (without an engine: the
             # float64 host k-means on the .emb text)
+            fits = []
             for i in range(2):
                 nce = ncl.NodeClusterEval(cfg.emb_filenames[i], cfg.labels_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i,
                                           k=int(_cfg(cfg, "engine_cluster_k", 0)), n_init=int(_cfg(cfg, "engine_cluster_n_init", 4)),
                                           max_iters=int(_cfg(cfg, "engine_cluster_max_iters", 100)), seed=self.seed)
                 results.append(ncl.format_results(cfg.modes[i], nce.eval_node_clustering()))
+                fits.append(nce.last_partition)
+            if _cfg(cfg, "engine_cluster_silhouette", False):
+                # exact silhouette over all pairs (gg_silhouette) of the partitions just reported and of the labels: one line per
+                # mode, "gen_sil:sil=<s> label_sil=<l> k=<k> n=<n> rows=<r> precision=<p>" (without an engine: float64 on the .emb text)
+                for i in range(2):
+                    emd = None if self.engine is not None else utils.read_embeddings(cfg.emb_filenames[i], n_node=self.n_node, n_embed=cfg.n_emb)
+                    nse = nsil.NodeSilhouetteEval(self.n_node, cfg.n_emb, engine=self.engine, emd=emd, which=i,
+                                                  precision=_cfg(cfg, "engine_sil_precision", "fp32"),
+                                                  max_rows=int(_cfg(cfg, "engine_sil_max_rows", 0)), seed=self.seed)
+                    fit = fits[i]
+                    results.append(nsil.format_results(cfg.modes[i], nse.eval_node_silhouette(fit["nodes"], fit["classes"], fit["assign"], fit["k"])))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

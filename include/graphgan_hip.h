@@ -566,6 +566,41 @@ int gg_kmeans_fit(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, int k
                   const int32_t *init_nodes /* [k] or NULL */, int32_t *assign_out, float *dist2_out, int32_t *counts_out,
                   double *inertia_out /* [max_iters] or NULL */, int32_t *iters_out, int32_t *converged_out, double *ms_out);
 
+/* ---- silhouette of a node partition (additive entry point; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour
+ * changes).  The exact silhouette coefficient over ALL pairs of the FROZEN rows x_i = E[nodes[i]] of table `which` under the
+ * partition c_i = assign[i] in [0, k), n_c = the size of cluster c; the label-free twin of the scores gg_kmeans_* is judged
+ * by.  A consumer of the matrix-core tile stream (gg_all_score_reduce, gg_topk_scores, gg_rank_scores): nothing of size m x m
+ * or m x n_emb crosses to the host.  For every evaluated position i, in fp32:
+ *   dist_ij = sqrtf(max(0, (h_i + h_j) - 2 s_ij)), the square root correctly rounded;
+ *             precision 0 (fp32): s_ij = the bits of gg_all_score's k-ordered fmaf chain of x_i . x_j, h_i = the same chain of
+ *               row i with itself;
+ *             precision 1 (bf16): s_ij = the bits of the bf16 stream (bf16 inputs, fp32 accumulate), h_i = the fp32 k-ordered
+ *               fmaf chain over the bf16-ROUNDED row: the silhouette of the bf16-rounded table, as gg_rank_scores' bf16 leg;
+ *   S_ic    = sum over j != i with c_j = c of dist_ij (fp32 sums in the implementation's fixed order); the own term is dropped
+ *             BY POSITION, not by a computed distance of 0
+ *   a_i     = S_{i, c_i} / (float)(n_{c_i} - 1)
+ *   b_i     = min over c != c_i with n_c > 0 of S_ic / (float)n_c,   nearest_i = that c, TIES TO THE LOWEST c
+ *   sil_i   = (b_i - a_i) / fmaxf(a_i, b_i);   n_{c_i} = 1: sil_i = 0 and a_i = 0 (the scikit-learn convention; b_i and nearest_i
+ *             are still those above);   fmaxf(a_i, b_i) = 0: sil_i = 0
+ *   mean    = (float64 sum of sil_i in output order) / count
+ * rows == NULL evaluates every position (outputs [m], in the order of `nodes`); otherwise the positions rows[t] into `nodes`
+ * (outputs [n_rows], entry t for rows[t]; a position MAY REPEAT, its entries are then equal), each against all m columns.
+ * Every output may be NULL.  ms_out: HIP-event time of the device work (copy, stream passes, finish).
+ * limits       2 <= k <= 128, 2 <= m <= 2^31 - 1, at least two non-empty clusters, node ids in [0, n_node) and DISTINCT, assign
+ *              in [0, k), rows in [0, m) with 1 <= n_rows <= 2^31 - 1, precision 0 or 1; the widths of the tile stream (fp32
+ *              n_emb <= 1116, bf16 n_emb <= 512).  Anything else: GG_EINVAL, the gg_last_error text names the limit, nothing
+ *              is launched.
+ * determinism  no floating-point atomics: the same inputs and table give the same bits.  The set is laid out sorted by
+ *              (cluster, node id), every sum runs over that layout, and the column split depends on the set alone, so the
+ *              outputs of a node do not depend on the order in which `nodes` lists the set (a permuted call returns the permuted
+ *              outputs bit for bit), and with `rows` every entry equals the full call's entry bit for bit.
+ * memory       the (row, cluster) stage is bounded by internal row passes of at most 4 096 rows (fewer for many clusters: at
+ *              most 64 MiB); temporary device buffers are freed on every exit path. */
+int gg_silhouette(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *assign, int64_t m, int k,
+                  const int64_t *rows /* [n_rows] positions into nodes, or NULL = all */, int64_t n_rows, int precision /* 0 fp32, 1 bf16 */,
+                  float *sil_out, float *a_out, float *b_out, int32_t *nearest_out /* each [n_rows or m] or NULL */,
+                  double *mean_out /* [1] or NULL */, double *ms_out);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
