@@ -250,11 +250,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // quad's registers are re-initialised with the bias of tile t + 1 (a ring of 4 bias tiles in LDS).  Tiles outside the split
 // have a bias of -inf: x = -inf, exp2 = 0, never a maximum -- the pipeline's first and last iterations need no special case.
 // Measured, 4 096 rows x 10^7 nodes x d = 256 (ms per call): 15.6 - 16.0 with the log-sum-exp (the 16x16x32 kernel: 21.2),
-// 14.3 - 14.6 without; its matrix instructions alone (ablation 27: no staging, no LDS reads) 11.2 -- the chip sustains ~1.9 GHz
+// 14.3 - 14.6 without; its matrix instructions alone (no staging, no LDS reads: profiles/HISTORY.md) 11.2 -- the chip sustains ~1.9 GHz
 // under this load (SQ_BUSY_CYCLES / duration), at which 6.4 10^8 matrix instructions x 32 cycles are 10.5 ms.
-// DBG (builds with -DGG_K7_ABLATIONS only; results WRONG): 1 no barrier / staging, 2 no table loads, 4 no argmax resolution, 8 no
-// fragment reads, 16 no bias reads, 128 staging through registers instead of LDS-DMA
-template <int KS, int RB, int NW, bool LSE, int DBG = 0>
+template <int KS, int RB, int NW, bool LSE>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4))) void all_score_reduce_bf16_x32_kernel(
     const uint4 *Eb, const float *bias, int n_node, const int32_t *rows, int n_rows, int cols_per_split, float *part_max, int32_t *part_arg,
     float *part_sum, int32_t *overflow) {
@@ -305,7 +303,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
         const int c = cbeg + 32 * t + tid;
         return (tid < 32 && t < n_tiles && c < cend) ? bias[c] : -INFINITY;
     };
-    constexpr bool DMA = (DBG & 128) == 0;  // LDS-DMA requests (default) or registers (measured: the same speed, 8 G registers more)
     u32x4 g[G];
     float gb;
     unsigned char *b_cur = x32_lds, *b_nxt = x32_lds + BUF, *b_n2 = x32_lds + 2 * BUF, *b_wr = x32_lds + 3 * BUF;  // tiles t .. t + 3
@@ -326,7 +323,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
 #pragma unroll
         for (int k = 0; k < G; ++k) g[k] = src[64 * k];
 #pragma unroll
-        for (int k = 0; k < G; ++k) if (stager && DMA) ((u32x4 *)b_n2)[(wv * G + k) * 64 + lane] = g[k];  // (!DMA: iteration 0 stores it)
+        for (int k = 0; k < G; ++k) if (stager) ((u32x4 *)b_n2)[(wv * G + k) * 64 + lane] = g[k];
         gb = bias_of(3);  // (iteration 0 stores it)
     }
     __syncthreads();
@@ -380,34 +377,28 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
 #pragma unroll
                 for (int k = 0; k < RB; ++k) {
                     const int slot = s * RB + k;
-                    if (s == KS / 2 && k == 0 && !(DBG & 1)) {
+                    if (s == KS / 2 && k == 0) {
                         // (the tile requested one iteration ago has landed: nothing to wait for; the wait makes it formal)
-                        if (DMA) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                        else asm volatile("s_barrier" ::: "memory");
+                        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
                     }
                     acc[p][k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s % RING].v, rf[k][s].v, acc[p][k], 0, 0, 0);
                     if (k == 0) {
 #pragma unroll
                         for (int e = 3; e < ELEMS; e += 4) {  // quads whose last element was consumed during the previous k-step
-                            if (s == 0 || e * CS / ELEMS < (s - 1) * RB || e * CS / ELEMS >= s * RB || (DBG & 16)) continue;
+                            if (s == 0 || e * CS / ELEMS < (s - 1) * RB || e * CS / ELEMS >= s * RB) continue;
                             const f32x4 b = bq[2 * ((e & 15) >> 2)];
 #pragma unroll
                             for (int j = 0; j < 4; ++j) acc[p ^ 1][e >> 4][(e & 12) + j] = b[j];
                         }
-                        if (!(DBG & 8)) af[(s + PD) % RING].q = s + PD < KS ? tl[64 * (s + PD)] : tl_next[64 * (s + PD - KS)];
+                        af[(s + PD) % RING].q = s + PD < KS ? tl[64 * (s + PD)] : tl_next[64 * (s + PD - KS)];
                     }
-                    if (DMA && k == (RB > 1 ? 1 : 0) && s >= KS / 2 && s < KS / 2 + G && stager && !(DBG & 3)) {
+                    if (k == (RB > 1 ? 1 : 0) && s >= KS / 2 && s < KS / 2 + G && stager) {
                         // tile t + 3 straight into the buffer tile t - 1 has left; lane l's 16 bytes land at M0 + 16 l
                         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(dsrc + 64 * (s - KS / 2)),
                                                          (void __attribute__((address_space(3))) *)(b_wr + (wv * G + s - KS / 2) * 1024), 16, 0, 0);
                     }
-                    if (!DMA && s >= KS / 2 && s < KS / 2 + G && stager && !(DBG & 1)) {
-                        // tile t + 2 (requested one iteration ago) into its buffer, and the same registers take tile t + 3
-                        if (k == (RB > 1 ? 1 : 0)) ((u32x4 *)b_n2)[(wv * G + s - KS / 2) * 64 + lane] = g[s - KS / 2];
-                        if (k == RB - 1 && !(DBG & 2)) g[s - KS / 2] = dsrc[64 * (s - KS / 2)];
-                    }
-                    if (k == 0 && s == KS / 2 && !(DBG & 1)) ring_dst[32 * ((t + 3) & 3)] = gb;  // bias of tile t + 3 (in front of the DMA requests)
-                    if (k == RB - 1 && s == KS / 2 + 1 && !(DBG & 3)) gb = bok ? bias[bc] : -INFINITY;  // ... of tile t + 4
+                    if (k == 0 && s == KS / 2) ring_dst[32 * ((t + 3) & 3)] = gb;  // bias of tile t + 3 (in front of the DMA requests)
+                    if (k == RB - 1 && s == KS / 2 + 1) gb = bok ? bias[bc] : -INFINITY;  // ... of tile t + 4
 #pragma unroll
                     for (int e = 0; e < ELEMS; ++e) {
                         if (e * CS / ELEMS != slot) continue;
@@ -449,7 +440,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4,
         const float m_o = __shfl_xor(rm[rb], 32, 64);
         const int t_o = __shfl_xor(rt[rb], 32, 64);
         const bool need = rt[rb] >= 0 && (rm[rb] > m_o || (rm[rb] == m_o && rt[rb] <= t_o));
-        unsigned long long todo = (DBG & 4) ? 0ull : __builtin_amdgcn_ballot_w64(need);
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(need);
         int arg = 0x7fffffff;
         while (todo) {
             const int j = __builtin_ctzll(todo);
@@ -613,26 +604,7 @@ static int reduce_once(gg_ctx *ctx, const int32_t *rows, int32_t n_rows, int32_t
                                d_pm.as<float>(), d_pa.as<int32_t>(), d_ps.as<float>(), d_ovf.as<int32_t>());                                             \
         }                                                                                                                                              \
     } while (0)
-#ifdef GG_K7_ABLATIONS  // (make EXTRA=-DGG_K7_ABLATIONS: the timing ablations of profiles/HISTORY.md, results WRONG)
-        static const int k7dbg = getenv("GG_K7_DBG") ? atoi(getenv("GG_K7_DBG")) : 0;
-#else
-        constexpr int k7dbg = 0;
-#endif
-        if (wide && k7dbg && KS == 16) {
-#ifdef GG_K7_ABLATIONS
-            const size_t dyn = 4 * 16 * 1024 + 1024 + 256 * 4;
-#define GG_X32_DBG(D)                                                                                                                         \
-    case D:                                                                                                                                   \
-        (void)hipFuncSetAttribute((const void *)all_score_reduce_bf16_x32_kernel<16, 4, 4, false, D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
-        hipLaunchKernelGGL((all_score_reduce_bf16_x32_kernel<16, 4, 4, false, D>), grid, dim3(256), dyn, ctx->stream, Eb, G.b, n, dr, n_rows, cps,    \
-                           d_pm.as<float>(), d_pa.as<int32_t>(), d_ps.as<float>(), d_ovf.as<int32_t>());                                        \
-        break;
-            switch (k7dbg) {
-                GG_X32_DBG(1) GG_X32_DBG(2) GG_X32_DBG(4) GG_X32_DBG(8) GG_X32_DBG(16) GG_X32_DBG(27) GG_X32_DBG(128)
-            }
-#undef GG_X32_DBG
-#endif
-        } else if (wide) {
+        if (wide) {
             if (KS <= 4) { GG_BF16_X32(4, 2, 8); }
             else if (KS <= 8) { GG_BF16_X32(8, 2, 8); }
             else if (KS <= 16) { if (one_wave) { GG_BF16_X32(16, 4, 4); } else { GG_BF16_X32(16, 2, 8); } }

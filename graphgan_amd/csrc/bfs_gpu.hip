@@ -58,8 +58,6 @@ struct BfsArgs {
     uint32_t *gbitmap;       // [grid][bm_words]  (graphs too large for the LDS bitmap)
     uint32_t *gkey;          // [grid][n_node]    all-ones between uses (duplicate-list overflow path)
     int bm_words;
-    int exp;                   // GG_BFS_EXPERIMENT: timing ablations (results are then WRONG): 1 = no cstart stores, 2 = synthetic targets instead of adjacency loads, 4 = no queue stores beyond level 1, 8 = no early exit when the component is complete, 64 = streaming stores for t_edge, 128 = nothing (the instrumented instance as its own baseline): results stay right with 8 / 64 / 128
-    unsigned long long *prof;  // GG_BFS_PROFILE: [32] shader-clock cycles of wave 0 per phase + event counts (NULL: off)
     // sparse levels (bfs_order2_kernel with the bitmap in LDS; see "SPARSE LEVEL" there): per-workgroup scratch
     int sp_k;                  // a level is expanded through its candidate fathers when unseen nodes * sp_k <= level nodes (< 0: never)
     int sp_min;                // ... and the level has at least this many nodes
@@ -89,14 +87,13 @@ struct BfsArgs {
     int64_t *base_w;           // [slots]   LAZY: t_base, written here
     int32_t *lz_flag;          // [slots]
     int lz_easy, lz_limit_easy;  // levels 1 .. lz_easy are expanded while they fit lz_limit_easy (>= the root's own limit)
-    int lz_ablate;             // GG_LZ_ABLATE (timing only, results WRONG): 1 = no rank scatter, 2 = no copy out of the scratch tree, 4 = no visited index; 8 (results right) = the ranks' indices from the index in global memory instead of LDS
 };
 
 __device__ __forceinline__ int lanes_below(unsigned long long m) {  // popcount of m restricted to the lanes below this one
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// What bounds the kernel (GG_BFS_PROFILE, rocprof SQ counters, GG_BFS_EXPERIMENT ablations): instruction issue.  The
+// What bounds the kernel (phase clocks, rocprof SQ counters and ablations in profiles/r2_bfs_notes.txt): instruction issue.  The
 // adjacency loads return within 3 % of the time (replacing them by computed targets saves a quarter), stores cost
 // nothing; 16 wavefronts share 4 SIMDs and one scalar unit, and every edge costs a map step, a load, a bit test and
 // its share of the compaction.  So the per-edge path is kept short: 8 consecutive stream positions per thread whose
@@ -105,9 +102,7 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {  // popcount 
 // chunks, most of the last two levels -- leave after one barrier.  (Measured and not kept: lane-consecutive positions
 // for fully coalesced loads, and a per-wave node-start bitmap instead of the map -- same speed or slower: more
 // instructions per edge, and the loads were never the limit.)
-// INSTR: the phase clocks (GG_BFS_PROFILE) and the ablation switches (GG_BFS_EXPERIMENT) are compiled into a second
-// instance only -- tested at run time in the production kernel they cost 10 % (85.7 -> 95.7 us per tree).
-template <bool LDS_BM, bool INSTR>
+template <bool LDS_BM>
 __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
     extern __shared__ uint32_t lds_bm[];           // [bm_words] when LDS_BM
     __shared__ int32_t eoff[BFS_NB + 1];           // exclusive scan of the batch's degrees
@@ -155,15 +150,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
         __syncthreads();
 
         int head = 0, tail = 1, level_end = 1, depth = 0;
-        // phase clocks of wave 0 (time to the barrier that ends the phase = what the whole workgroup waited for)
-        unsigned long long pc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        long long tprev = (INSTR && a.prof) ? (long long)clock64() : 0;
-#define BFS_TICK(k)                                             \
-    if (INSTR && a.prof) {                                      \
-        const long long tn = (long long)clock64();              \
-        pc[k] += (unsigned long long)(tn - tprev);              \
-        tprev = tn;                                             \
-    }
         int pf_q = -1;          // queue index whose node this thread has prefetched for the NEXT batch
         uint32_t pf_e0 = 0;
         int pf_deg = 0;
@@ -197,7 +183,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
             if (lane == 63) wave_tot[wv] = inc;
             if (tid == 0) { s_cap = 0; s_fb = BFS_NB; }
             __syncthreads();
-            BFS_TICK(0)  // node info + scan
             int pre = 0;
 #pragma unroll
             for (int i = 0; i < BFS_WAVES; ++i)
@@ -235,8 +220,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                 }
             }
             __syncthreads();
-            BFS_TICK(1)  // batch formation, map fill, prefetch issue
-            pc[8] += 1;
             const int TE = eoff[nb];
 
             // ---- the batch's edge stream, BFS_CH positions at a time
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                                 e = e0s[idx];
                                 nextb = eoff[idx + 1];
                             }
-                            w[j] = (INSTR && (a.exp & 2)) ? (int)((e * 2654435761u) % (uint32_t)a.n_node) : a.col[e];
+                            w[j] = a.col[e];
                             ++e;
                             vmask |= 1u << j;
                             if (p + 1 == nextb) lmask |= 1u << j;
@@ -273,8 +256,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                 const int slot = (int)(chunk_no % 3u);
                 if (__ballot(cmask != 0u) && lane == 0) s_any[slot] = 1;
                 __syncthreads();  // every test before any set: a later edge must not hide an earlier one
-                BFS_TICK(2)  // map, adjacency loads, tests
-                pc[9] += 1;
                 if (tid == 0) s_any[(slot + 2) % 3] = 0;  // the previous chunk's flag: everyone is past reading it
                 if (!s_any[slot]) {
                     // nothing new in this chunk: every node that ends here has its children end at `tail`
@@ -282,10 +263,8 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                     while (lm) {
                         const int j = __ffs(lm) - 1;
                         lm &= lm - 1;
-                        if (!(INSTR && (a.exp & 1))) cstart[head + qfirst + __popc(lmask & ((1u << j) - 1u)) + 1] = tail;
+                        cstart[head + qfirst + __popc(lmask & ((1u << j) - 1u)) + 1] = tail;
                     }
-                    BFS_TICK(3)  // chunk without new nodes
-                    pc[10] += 1;
                     continue;
                 }
                 uint32_t hmask = 0;  // this edge cleared -> set the bit (the hardware winner among the chunk's edges to its node)
@@ -303,9 +282,7 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                     }
                 }
                 __syncthreads();
-                BFS_TICK(4)  // claim
                 const int nL = Lcount;
-                if (nL > 0) pc[11] += 1;
                 uint32_t mine = hmask;  // positions that append their target; without in-chunk duplicates: the winners themselves
                 if (nL > 0) {
                     if (nL <= BFS_LCAP) {
@@ -341,7 +318,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                             if ((cmask >> j) & 1u) __hip_atomic_store(&gkey[w[j]], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                     __syncthreads();
-                    BFS_TICK(5)  // duplicate resolution
                     mine = (winbits[(BFS_U * tid) >> 5] >> ((BFS_U * tid) & 31)) & ((1u << BFS_U) - 1u);
                 }
                 // ---- the appending positions, in stream order, are the next queue entries
@@ -354,7 +330,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                 }
                 if (lane == 0) wave_cnt[wv] = wtotal;
                 __syncthreads();
-                BFS_TICK(6)  // in-wave compaction
                 int wpre = 0, total = 0;
 #pragma unroll
                 for (int i = 0; i < BFS_WAVES; ++i) {
@@ -383,7 +358,7 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                         }
                         ++e2;
                         if ((lmask >> j) & 1u) {  // children of this queue node end here
-                            if (!(INSTR && (a.exp & 1))) cstart[q] = rank;
+                            cstart[q] = rank;
                             ++q;
                         }
                     }
@@ -393,7 +368,6 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
                     if (tid < BFS_CH / 32) winbits[tid] = 0u;
                     if (tid == 0) Lcount = 0;
                 }
-                BFS_TICK(7)  // queue / cstart stores issued
                 if (tail > expect) break;  // more nodes than the component sweep promised: the graph is not the one set (uniform)
             }
             if (tail > expect) break;
@@ -403,16 +377,13 @@ __global__ __launch_bounds__(BFS_T) void bfs_order_kernel(const BfsArgs a) {
             // the nodes still waiting can discover anything.  On a small-world graph that is the bulk of the stream -- the
             // last two levels hold most nodes and found nothing in half of all chunks -- so their adjacency is not read at
             // all: they are leaves of the tree (their child ranges are empty, at the end of the queue).
-            if (tail == expect && head < tail && !(INSTR && (a.exp & 8))) {
+            if (tail == expect && head < tail) {
                 for (int i = head + tid; i < expect; i += BFS_T) cstart[i + 1] = expect;
                 if (level_end < tail) ++depth;  // the nodes behind level_end are one level deeper than the one being popped
                 __syncthreads();                // (the child-count sweep below reads these entries)
                 break;
             }
         }
-        if (INSTR && a.prof && tid == 0)
-            for (int k = 0; k < 12; ++k) atomicAdd(&a.prof[k], pc[k]);
-#undef BFS_TICK
 
         // ---- per-root results: node count check, depth, longest list (1 + most children)
         int mc = 0;
@@ -491,25 +462,17 @@ typedef int32_t __attribute__((address_space(3))) lds_i32_t;
 
 // SPARSE LEVEL of bfs_order2_kernel (see there): the candidate fathers S of the level [lo, hi) of one root's queue, ascending, into
 // `slist`; returns their number, or -1 if the unseen nodes do not fit the scratch (nothing has changed then).  On return the LDS
-// bitmap `bm` is the visited bitmap again, cstart[lo + 1 .. hi] is zero, and wtot[16] / wtot[17] hold the unseen nodes listed and
-// the bucket passes made (profile).  A function of its own (not inlined): its registers must not compete with the window loop's
-// (inlined, the kernel spilled 84-172 VGPRs, some inside the window loop).  Called by all 1 024 threads of the workgroup.
+// bitmap `bm` is the visited bitmap again and cstart[lo + 1 .. hi] is zero.  A function of its own (not inlined): its registers
+// must not compete with the window loop's (inlined, the kernel spilled 84-172 VGPRs, some inside the window loop).  Called by
+// all 1 024 threads of the workgroup.
 // Every loop keeps several independent loads in flight per thread -- a workgroup alone on its CU hides no latency by itself:
 // written as plain one-load-per-iteration loops the search cost 9 M cycles per tree, more than the level popped whole.
-template <bool INSTR>
-__device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t *bm, lds_i32_t *wtot, lds_i32_t *s_live, const uint32_t *__restrict__ rowptr32,
+__device__ __forceinline__ int sparse_fathers(lds_u32_t *bm, lds_i32_t *wtot, lds_i32_t *s_live, const uint32_t *__restrict__ rowptr32,
                                            const int32_t *__restrict__ col, const int32_t *order, int32_t *cstart, int32_t *ux, unsigned long long *ui,
                                            unsigned long long *slist, uint32_t *vis, uint32_t *mark, unsigned long long *smask, int n_node, int W, int sp_cap,
                                            int NBK, int lo, int hi, int Un) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int F = hi - lo;
-    long long tprev = INSTR ? (long long)clock64() : 0;  // phase clocks (GG_BFS_PROFILE): list, cstart zeros, bucket bitmap, scan, restore, rank masks, S list
-#define SP_TICK(k)                                  \
-    if (INSTR) {                                    \
-        const long long tn = (long long)clock64();  \
-        sph[k] += (unsigned long long)(tn - tprev); \
-        tprev = tn;                                 \
-    }
     const uint32_t lastmask = (n_node & 31) ? (1u << (n_node & 31)) - 1u : 0xffffffffu;
     // unseen nodes: count (the bitmap is saved on the way), list
     int zc = 0;
@@ -556,11 +519,9 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
         for (int u = 0; u < 4; ++u)
             if (xs[u] >= 0) ui[idx0 + u * B2_T] = (unsigned long long)rp[u].x | ((unsigned long long)(rp[u].y - rp[u].x) << 32);
     }
-    SP_TICK(0)
     for (int i = lo + 1 + tid; i <= hi; i += B2_T) cstart[i] = 0;
     if (tid == 0) *s_live = 0;
     __syncthreads();
-    SP_TICK(1)
     const int bs = (F + NBK - 1) / NBK;
     int jdone = 0;
     int L = nU;  // unseen nodes not served yet: a dense list, rewritten by every pass
@@ -586,7 +547,6 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
                 if (vv[u] >= 0) (void)__hip_atomic_fetch_or(&bm[vv[u] >> 5], 1u << (vv[u] & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         lds_barrier();
-        SP_TICK(2)
         // Four lanes per list entry, one quad each (the entry's adjacency is one or two cache lines: a wave's load touches ~20
         // lines; with a lane per entry it touched 64, and the CU's L1 path -- 2-3 cycles per line of a fully divergent load --
         // was the whole scan); four entries per group and round in flight, the next round's entries under them (eight: registers spill, 3.4 -> 5 M cycles).
@@ -657,7 +617,6 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
         jdone = j + 1;
         lds_barrier();  // (everyone has read the count)
         if (tid == 0) *s_live = 0;
-        SP_TICK(3)
     }
     // the marks into LDS (and cleared in global memory): S by rank is 0.75 M bit tests in rank order
     for (int i0 = tid; i0 < W; i0 += 8 * B2_T) {
@@ -672,7 +631,6 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
             }
     }
     lds_barrier();
-    SP_TICK(4)
     // S by rank: the level's ranks up to the last bucket used, a contiguous share per wavefront
     const long long cend_l = (long long)lo + (long long)jdone * bs;
     const int cend = cend_l < (long long)hi ? (int)cend_l : hi;
@@ -698,7 +656,6 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
     }
     if (lane == 0) wtot[wv] = scount;
     __syncthreads();  // the masks have landed; every mark has been read
-    SP_TICK(5)
     int spre = 0, stot = 0;
 #pragma unroll
     for (int i = 0; i < B2_WAVES; ++i) {
@@ -726,7 +683,6 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
             pos += (int)__popcll(ms[u]);
         }
     }
-    if (tid == 0) { wtot[16] = nU; wtot[17] = jdone; }
     __syncthreads();
     for (int p0 = tid; p0 < stot; p0 += 8 * B2_T) {  // ... and their node ids beside the ranks (what the windows' prefetch starts from)
         int rk[8], vv[8];
@@ -739,17 +695,14 @@ __device__ __forceinline__ int sparse_fathers(unsigned long long *sph, lds_u32_t
             if (rk[u] >= 0) slist[p0 + u * B2_T] = (unsigned long long)(uint32_t)rk[u] | ((unsigned long long)(uint32_t)vv[u] << 32);
     }
     __syncthreads();
-    SP_TICK(6)
-#undef SP_TICK
     return stot;
 }
 
-// INSTR: the phase clocks (GG_BFS_PROFILE), event counts and ablation switches (GG_BFS_EXPERIMENT) live in a second instance only.
 // LAZY (round 6): the tree is built exactly only through the last level whose expansion is KNOWN to fit the slot's node limit
 // (nodes so far + adjacency entries of the level's nodes <= limit: every entry could append a node); the children lists of that
 // level and below are resolved by the walks that need them (walk_sample.hip, "LAZY").  The kernel then leaves what resolution
 // needs: the visited set of the exact levels with a popcount index, and the BFS rank of every member by that index.
-template <bool LDS_BM, bool INSTR, bool LAZY = false>
+template <bool LDS_BM, bool LAZY = false>
 __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_bm[];  // [bm_words, rounded up to 16] when LDS_BM
     __shared__ uint32_t e0s[B2_NB];                   // first CSR entry of each window node (of the segment, for a partial node)
@@ -807,17 +760,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
 
         int head = 0, tail = 1, level_end = 1, depth = 0;
         int fenced = 1;          // queue entries below this index were written before the last full fence
-        unsigned long long st_win = 0, st_fence = 0, st_cand = 0, st_slots = 0, st_empty = 0, st_dup = 0, st_key = 0;  // GG_BFS_PROFILE
-        unsigned long long st_sp = 0, st_spu = 0, st_sps = 0, st_spp = 0;  // sparse levels, unseen nodes listed, candidate fathers, passes
-        unsigned long long sph[7] = {0, 0, 0, 0, 0, 0, 0};  // phases of the father search
-        unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // wave 0's clock per phase: setup, scan, claim, duplicates, prefix, append; [8] sparse-level build, [9] its cstart fill
-        long long tprev = INSTR ? (long long)clock64() : 0;
-#define B2_TICK(k)                                  \
-    if (INSTR) {                                    \
-        const long long tn = (long long)clock64();  \
-        ph[k] += (unsigned long long)(tn - tprev);  \
-        tprev = tn;                                 \
-    }
         int seg_a = 0;           // > 0: the node at `head` is being scanned in segments, this many entries are done
         int pf_q = -1;           // queue index whose node this thread has prefetched
         // THE PREFETCH of the next window's nodes is a chain node id -> row offsets -> degree (a sparse level's list carries the id
@@ -947,7 +889,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
             if (!smode && fenced < tail && head + 2 * B2_NB > fenced) {
                 __syncthreads();
                 fenced = tail;
-                if (INSTR) ++st_fence;
             }
             int nb = 0;      // complete nodes of this window; 0 = one node, entries [seg_a, seg_a + seg_len)
             int seg_len = 0;
@@ -983,7 +924,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 if (lane == 63) wtot[0][wv] = incq;
                 if (tid == 0) { s_cap = 0; s_e0 = e0; s_deg = deg; }
                 lds_barrier();
-                B2_TICK(0)
                 int preq = 0;
 #pragma unroll
                 for (int i = 0; i < B2_WAVES; ++i)
@@ -993,7 +933,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 const unsigned long long okb = __ballot(tid < navail && inclq <= B2_SLOTS);
                 if (lane == 0 && okb) atomicAdd(&s_cap, (int)__popcll(okb));
                 lds_barrier();
-                B2_TICK(1)
                 nb = s_cap;
                 if (nb > 0) {
                     if (tid < nb) {
@@ -1035,11 +974,8 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 }
             }
             lds_barrier();
-            B2_TICK(2)
             const int nbn = nb > 0 ? nb : 1;  // window nodes
             const int T = (int)soff[nbn];
-            if (INSTR) ++st_win;
-            if (INSTR) st_slots += (unsigned long long)T;
 
             // ---------------- SCAN: quads tid, tid + 1024, ...; position of entry k of quad s = 4 s + k (stream order)
             int4u w4[4];
@@ -1062,13 +998,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
             }
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
-                if (INSTR && (a.exp & 2)) {  // (ablation: computed targets instead of the adjacency loads)
-                    const uint32_t hx = we[it] * 2654435761u;
-                    w4[it].x = (int)(hx % (uint32_t)a.n_node); w4[it].y = (int)((hx >> 3) % (uint32_t)a.n_node);
-                    w4[it].z = (int)((hx >> 5) % (uint32_t)a.n_node); w4[it].w = (int)((hx >> 7) % (uint32_t)a.n_node);
-                } else {
-                    w4[it] = *reinterpret_cast<const int4u *>(a.col + we[it]);
-                }
+                w4[it] = *reinterpret_cast<const int4u *>(a.col + we[it]);
             }
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
@@ -1089,18 +1019,15 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 }
             }
             if (__ballot(anyc != 0u) && lane == 0) s_any = 1;
-            B2_TICK(3)
             lds_barrier();  // every test before any set: a later edge must not hide an earlier one
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), stated where the compiler sees it (free: the scan has just used its loads): see "THE PREFETCH"
             if (pf_stage == 2) {  // second link: the row offsets (the id arrived under the scan)
                 pf_rp = *reinterpret_cast<const uint2u *>(a.rowptr32 + (smode ? (int)(pf_sl >> 32) : pf_v));
                 pf_stage = 3;
             }
-            B2_TICK(4)
 
             if (!s_any) {
                 // nothing new: every node that ends in this window has its children end at `tail`
-                if (INSTR) ++st_empty;
                 if (nb > 0) {
                     if (tid < nb) cstart[my_rk + 1] = tail;
                     head += nb;
@@ -1144,7 +1071,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                     }
                 }
                 lds_barrier();
-                B2_TICK(5)
                 const int nL = s_Lcount;
                 if (nL <= B2_DCAP) {
                     // the sequential BFS appends a node at the FIRST edge that reaches it: smallest position among the hardware
@@ -1156,7 +1082,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                             const int k = __ffs((int)c) - 1;
                             c &= c - 1u;
                             int eff = 4 * (tid + it * B2_T) + k;
-                            if (nL > 0 && !(INSTR && (a.exp & 16))) {
+                            if (nL > 0) {
                                 const int w = k == 0 ? w4[it].x : k == 1 ? w4[it].y : k == 2 ? w4[it].z : w4[it].w;
                                 uint32_t h = ((uint32_t)w * 2654435761u) >> 22;
                                 for (;;) {
@@ -1171,7 +1097,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                     }
                 } else {
                     // too many duplicates for the list: smallest position per node through the key array (all-ones between uses)
-                    if (INSTR) ++st_key;
 #pragma unroll
                     for (int it = 0; it < 4; ++it) {
                         uint32_t c = cand[it];
@@ -1206,7 +1131,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                         }
                     }
                 }
-                if (INSTR && nL > 0) ++st_dup;
                 lds_barrier();
                 // place of every appending position in stream order = popcount prefix over the mask
                 const int wcnt = tid < B2_WORDS ? (int)__popc(winbits[tid]) : 0;
@@ -1228,8 +1152,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                     pf_deg = (int)(pf_rp.y - pf_rp.x);
                     pf_stage = 0;
                 }
-                B2_TICK(6)
-                if (INSTR) st_cand += (unsigned long long)total;
                 // append: every candidate (hardware winner or duplicate) whose position carries the bit
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
@@ -1243,8 +1165,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                             const int rank = tail + wpre[p >> 5] + (int)__popc(word & ((1u << (p & 31)) - 1u));
                             if (rank < expect) {
                                 order[rank] = k == 0 ? w4[it].x : k == 1 ? w4[it].y : k == 2 ? w4[it].z : w4[it].w;
-                                if (INSTR && (a.exp & 64)) __builtin_nontemporal_store((int32_t)(we[it] + (uint32_t)k), &tedge[rank]);  // (ablation: streaming stores for the array nobody reads back)
-                                else tedge[rank] = (int32_t)(we[it] + (uint32_t)k);
+                                tedge[rank] = (int32_t)(we[it] + (uint32_t)k);
                             }
                         }
                     }
@@ -1273,10 +1194,9 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 if (tail > expect) break;  // more nodes than the component sweep promised: the graph is not the one set (uniform)
             }
             lds_barrier();
-            B2_TICK(7)
             // Every node of the root's component is on the queue (its size is known from the component sweep): no edge of the
             // nodes still waiting can discover anything -- they are leaves of the tree (empty child ranges at the end of the queue).
-            if (tail == expect && (smode || head < tail) && !(INSTR && (a.exp & 8))) {
+            if (tail == expect && (smode || head < tail)) {
                 why = 3;
                 break;
             }
@@ -1285,7 +1205,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
           if (why == 1) {
               __syncthreads();  // the level's queue entries have landed: the search reads them back
               fenced = tail;
-              const int got = sparse_fathers<INSTR>(sph, (lds_u32_t *)bm, (lds_i32_t *)&wtot[0][0], (lds_i32_t *)&s_live, a.rowptr32, a.col, order, cstart,
+              const int got = sparse_fathers((lds_u32_t *)bm, (lds_i32_t *)&wtot[0][0], (lds_i32_t *)&s_live, a.rowptr32, a.col, order, cstart,
                                              a.sp_ux + (size_t)blockIdx.x * a.sp_cap * 2, a.sp_ui + (size_t)blockIdx.x * a.sp_cap * 2, slist,
                                              a.sp_vis + (size_t)blockIdx.x * a.bm_words, a.sp_mark + (size_t)blockIdx.x * a.bm_words,
                                              a.sp_mask + (size_t)blockIdx.x * ((size_t)a.n_node / 64 + 32), a.n_node, a.bm_words, a.sp_cap, a.sp_buckets,
@@ -1297,19 +1217,11 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                   s_hi = tail;
                   head = 0;
                   pf_q = -1;
-                  if (INSTR) {
-                      ++st_sp;
-                      st_spu += (unsigned long long)wtot[1][0];
-                      st_spp += (unsigned long long)wtot[1][1];
-                      st_sps += (unsigned long long)got;
-                  }
               }  // (else: the level is popped whole -- level_end has moved on, the test above does not fire again)
-              B2_TICK(8)
               continue;
           }
           if (why == 2) {
               fill_level(s_lo, s_hi);
-              B2_TICK(9)
               head = s_hi;
               smode = false;
               pf_q = -1;
@@ -1328,14 +1240,6 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
           break;
         }
         __syncthreads();  // (all queue / cstart stores have landed: the child-count sweep below reads cstart)
-        if (INSTR && a.prof && tid == 0) {
-            atomicAdd(&a.prof[0], st_win); atomicAdd(&a.prof[1], st_fence); atomicAdd(&a.prof[2], st_cand); atomicAdd(&a.prof[3], st_slots);
-            atomicAdd(&a.prof[4], st_empty); atomicAdd(&a.prof[5], st_dup); atomicAdd(&a.prof[6], st_key); atomicAdd(&a.prof[7], st_sp);
-            for (int k = 0; k < 10; ++k) atomicAdd(&a.prof[8 + k], ph[k]);
-            atomicAdd(&a.prof[18], st_spu); atomicAdd(&a.prof[19], st_sps); atomicAdd(&a.prof[20], st_spp);
-            for (int k = 0; k < 7; ++k) atomicAdd(&a.prof[21 + k], sph[k]);
-        }
-#undef B2_TICK
         const bool lazy_stop = LAZY && why == 4;  // ranks [head, tail) are level `depth`: exact queue entries without children lists
         if (LAZY) {
             // the slot's place in the tree arrays: exact ranks (+ pool), built lists; then the copy out of the scratch tree
@@ -1349,7 +1253,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
             }
             __syncthreads();  // (also: every queue / cstart store of the scratch tree has landed)
             const long long off = s_off;
-            if (off >= 0 && !(a.lz_ablate & 2)) {
+            if (off >= 0) {
                 int32_t *const o_out = a.order + off, *const e_out = a.edge + off, *const c_out = a.cstart + off;
                 for (int i0 = tid; i0 < n_keep; i0 += 4 * B2_T) {
                     int vo[4], ve[4];
@@ -1367,7 +1271,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 }
                 for (int i = tid; i <= n_built; i += B2_T) c_out[i] = ldi(&cstart[i]);
             }
-            if (lazy_stop && off >= 0 && !(a.lz_ablate & 4)) {
+            if (lazy_stop && off >= 0) {
                 // the visited set of the exact levels with its popcount index: {word, members below the word}
                 uint2 *const zb = a.lz_bm + (size_t)slot * a.bm_words;
                 int32_t *const zr = a.lz_rank + off;
@@ -1383,7 +1287,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 for (int i = 0; i < B2_WAVES; ++i)
                     if (i < wv) run += wtot[0][i];
                 // (members below every 16th word stay in LDS -- the windows' quad map is free now -- for the ranks' indices below)
-                const bool coarse = LDS_BM && (W + 15) / 16 <= B2_SLOTS / 2 && !(a.lz_ablate & 8);
+                const bool coarse = LDS_BM && (W + 15) / 16 <= B2_SLOTS / 2;
                 for (int i = w0; i < w1; ++i) {
                     const uint32_t wd = LDS_BM ? bm[i] : ldu(&bm[i]);
                     zb[i] = make_uint2(wd, (uint32_t)run);
@@ -1392,13 +1296,13 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                 }
                 __syncthreads();  // (the index has landed: the ranks below read it back)
                 // rank of every member by its index.  A member's index is as good as random: written straight to memory every 4-byte
-                // store is a read-modify-write of its own line -- 25 of the kernel's 46 ms per 16 384 roots (timing ablation,
-                // GG_LZ_ABLATE=1; the PMC counters charge the kernel 17 MB of HBM traffic per root).  So: the indices once, in queue
+                // store is a read-modify-write of its own line -- 25 of the kernel's 46 ms per 16 384 roots (timing ablation
+                // without the scatter, profiles/HISTORY.md; the PMC counters charge the kernel 17 MB of HBM traffic per root).  So: the indices once, in queue
                 // order, into the scratch row of first-child ranks (copied out above: free); then the index space through the LDS
                 // -- the bitmap's words are in `zb` now -- in blocks of W entries, each block one coalesced pass over the indices
                 // and one coalesced flush.  (Looking the index up again in every block pass instead: 61 ms.)
                 int32_t *const idxs = cstart;
-                for (int i0 = tid; i0 < tail && !(a.lz_ablate & 1); i0 += 8 * B2_T) {
+                for (int i0 = tid; i0 < tail; i0 += 8 * B2_T) {
                     int vv[8];
                     unsigned long long wq[8];
 #pragma unroll
@@ -1435,7 +1339,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
                         else zr[idx] = i0 + u * B2_T;
                     }
                 }
-                if (LDS_BM && !(a.lz_ablate & 1)) {
+                if (LDS_BM) {
                     __syncthreads();
                     for (int blk0 = 0; blk0 < tail; blk0 += W) {
                         for (int i0 = tid; i0 < tail; i0 += 8 * B2_T) {
@@ -1472,7 +1376,7 @@ __global__ __launch_bounds__(B2_T) void bfs_order2_kernel(const BfsArgs a) {
         // ---- per-root results: node count check, depth, longest list (1 + most children)
         int mc = 0;
         const int n_lists = lazy_stop ? head : tail;  // ranks whose children lists are built
-        if ((tail == expect || lazy_stop) && !(INSTR && (a.exp & 32)) && !LAZY)  // (LAZY: a resolved list is as long as a degree; the host takes the graph's largest)
+        if ((tail == expect || lazy_stop) && !LAZY)  // (LAZY: a resolved list is as long as a degree; the host takes the graph's largest)
             for (int i0 = tid; i0 < n_lists; i0 += 8 * B2_T) {  // (eight positions per thread in flight: 977 one-load iterations otherwise)
                 int c0[8], c1[8];
 #pragma unroll
@@ -1513,7 +1417,7 @@ static int bfs_run(gg_ctx *ctx, BfsArgs &a, int n_items, bool lazy, int32_t *sta
     // static LDS of the kernel (eoff, e0s, duplicate list, mask, counters) ~ 21.5 KB; the CU has 160 KB
     const bool v1 = getenv("GG_BFS_V1") != nullptr && !lazy && !a.expect;  // the chunk kernel of rounds 2-3 (kept for A/B timing and as a second witness in the tests)
     hipFuncAttributes fa;
-    GG_HIP(ctx, hipFuncGetAttributes(&fa, v1 ? (const void *)bfs_order_kernel<true, false> : (const void *)bfs_order2_kernel<true, false>));
+    GG_HIP(ctx, hipFuncGetAttributes(&fa, v1 ? (const void *)bfs_order_kernel<true> : (const void *)bfs_order2_kernel<true>));
     const size_t lds_total = 160 * 1024;
     const bool lds_bm = !getenv("GG_BFS_GLOBAL_BITMAP") && fa.sharedSizeBytes + (size_t)bm_words * 4 <= lds_total;
 
@@ -1531,7 +1435,7 @@ static int bfs_run(gg_ctx *ctx, BfsArgs &a, int n_items, bool lazy, int32_t *sta
     const size_t key_bytes_before = gkey.bytes;
     hipError_t e = gkey.reserve(sizeof(uint32_t) * (size_t)grid * n);
     if (e == hipSuccess && !lds_bm) e = gbm.reserve(sizeof(uint32_t) * (size_t)grid * bm_words);
-    constexpr size_t misc_bytes = sizeof(int32_t) * 8 + sizeof(unsigned long long) * 32;
+    constexpr size_t misc_bytes = sizeof(int32_t) * 8;
     if (e == hipSuccess) e = misc.reserve(misc_bytes);
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "gg_build_trees_device: scratch: %s", hipGetErrorString(e));
     // sparse levels (bfs_order2_kernel, LDS bitmap): GG_BFS_SPARSE=0 switches them off; _K / _MIN / _BUCKETS tune the choice
@@ -1565,9 +1469,6 @@ static int bfs_run(gg_ctx *ctx, BfsArgs &a, int n_items, bool lazy, int32_t *sta
     a.gbitmap = gbm.as<uint32_t>();
     a.gkey = gkey.as<uint32_t>();
     a.bm_words = bm_words;
-    const bool prof = getenv("GG_BFS_PROFILE") != nullptr && !lazy;
-    a.exp = (getenv("GG_BFS_EXPERIMENT") && !lazy) ? atoi(getenv("GG_BFS_EXPERIMENT")) : 0;
-    a.prof = prof ? (unsigned long long *)(misc.as<int32_t>() + 8) : nullptr;
     a.sp_k = sp_k;
     a.sp_min = sp_min;
     a.sp_buckets = sp_buckets;
@@ -1588,78 +1489,33 @@ static int bfs_run(gg_ctx *ctx, BfsArgs &a, int n_items, bool lazy, int32_t *sta
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     if (!v1) {
         const size_t dyn = lds_bm ? (size_t)((bm_words + 15) & ~15) * 4 : 0;  // (rounded up: the lazy finalize reads 16-word blocks)
-        const bool instr = prof || a.exp != 0;
-        const void *fn = lazy ? (lds_bm ? (const void *)bfs_order2_kernel<true, false, true> : (const void *)bfs_order2_kernel<false, false, true>)
-                         : lds_bm ? (instr ? (const void *)bfs_order2_kernel<true, true> : (const void *)bfs_order2_kernel<true, false>)
-                                  : (instr ? (const void *)bfs_order2_kernel<false, true> : (const void *)bfs_order2_kernel<false, false>);
+        const void *fn = lazy ? (lds_bm ? (const void *)bfs_order2_kernel<true, true> : (const void *)bfs_order2_kernel<false, true>)
+                              : (lds_bm ? (const void *)bfs_order2_kernel<true> : (const void *)bfs_order2_kernel<false>);
         if (lds_bm) {
             e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
             if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_build_trees_device: %zu bytes of LDS: %s", dyn, hipGetErrorString(e));
         }
-        if (lazy && lds_bm) hipLaunchKernelGGL((bfs_order2_kernel<true, false, true>), dim3(grid), dim3(B2_T), dyn, ctx->stream, a);
-        else if (lazy) hipLaunchKernelGGL((bfs_order2_kernel<false, false, true>), dim3(grid), dim3(B2_T), 0, ctx->stream, a);
-        else if (lds_bm && instr) hipLaunchKernelGGL((bfs_order2_kernel<true, true>), dim3(grid), dim3(B2_T), dyn, ctx->stream, a);
-        else if (lds_bm) hipLaunchKernelGGL((bfs_order2_kernel<true, false>), dim3(grid), dim3(B2_T), dyn, ctx->stream, a);
-        else if (instr) hipLaunchKernelGGL((bfs_order2_kernel<false, true>), dim3(grid), dim3(B2_T), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((bfs_order2_kernel<false, false>), dim3(grid), dim3(B2_T), 0, ctx->stream, a);
+        if (lazy && lds_bm) hipLaunchKernelGGL((bfs_order2_kernel<true, true>), dim3(grid), dim3(B2_T), dyn, ctx->stream, a);
+        else if (lazy) hipLaunchKernelGGL((bfs_order2_kernel<false, true>), dim3(grid), dim3(B2_T), 0, ctx->stream, a);
+        else if (lds_bm) hipLaunchKernelGGL((bfs_order2_kernel<true>), dim3(grid), dim3(B2_T), dyn, ctx->stream, a);
+        else hipLaunchKernelGGL((bfs_order2_kernel<false>), dim3(grid), dim3(B2_T), 0, ctx->stream, a);
     } else if (lds_bm) {
         const size_t dyn = (size_t)((bm_words + 15) & ~15) * 4;
-        const bool instr = prof || a.exp != 0;
-        const void *fn = instr ? (const void *)bfs_order_kernel<true, true> : (const void *)bfs_order_kernel<true, false>;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        e = hipFuncSetAttribute((const void *)bfs_order_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_build_trees_device: %zu bytes of LDS: %s", dyn, hipGetErrorString(e));
-        if (instr) hipLaunchKernelGGL((bfs_order_kernel<true, true>), dim3(grid), dim3(BFS_T), dyn, ctx->stream, a);
-        else hipLaunchKernelGGL((bfs_order_kernel<true, false>), dim3(grid), dim3(BFS_T), dyn, ctx->stream, a);
-    } else if (prof || a.exp != 0) {
-        hipLaunchKernelGGL((bfs_order_kernel<false, true>), dim3(grid), dim3(BFS_T), 0, ctx->stream, a);
+        hipLaunchKernelGGL((bfs_order_kernel<true>), dim3(grid), dim3(BFS_T), dyn, ctx->stream, a);
     } else {
-        hipLaunchKernelGGL((bfs_order_kernel<false, false>), dim3(grid), dim3(BFS_T), 0, ctx->stream, a);
+        hipLaunchKernelGGL((bfs_order_kernel<false>), dim3(grid), dim3(BFS_T), 0, ctx->stream, a);
     }
     (void)hipEventRecord(ctx->ev1, ctx->stream);
     for (int i = 0; i < 6; ++i) stats[i] = 0;
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(stats, a.stats, sizeof(int32_t) * 6, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && prof && !v1) {
-        const int n_roots = n_items;
-        unsigned long long pc[32];
-        if (hipMemcpy(pc, a.prof, sizeof(pc), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "[bfs2 profile] %d roots, grid %d: per root %.0f windows (%.0f without a candidate, %.0f with in-window duplicates, %.0f through the key array), "
-                    "%.1f full fences, %.0f nodes appended, %.0f quads scanned\n", n_roots, grid, (double)pc[0] / n_roots, (double)pc[4] / n_roots, (double)pc[5] / n_roots,
-                    (double)pc[6] / n_roots, (double)pc[1] / n_roots, (double)pc[2] / n_roots, (double)pc[3] / n_roots);
-            fprintf(stderr, "[bfs2 profile] sparse levels (k %d, min %d, %d buckets): %.2f per root, %.0f unseen nodes listed, %.1f bucket passes, %.0f candidate fathers per root\n",
-                    sp_k, sp_min, sp_buckets, (double)pc[7] / n_roots, (double)pc[18] / n_roots, (double)pc[20] / n_roots, (double)pc[19] / n_roots);
-            const char *names[10] = {"setup: node info + scan", "window choice", "quad map", "scan: loads + tests", "scan barrier", "claim", "duplicates + prefix",
-                                     "append + cstart (empty windows: all behind the scan)", "sparse level: father search", "sparse level: cstart fill"};
-            double tot = 0;
-            for (int k = 0; k < 10; ++k) tot += (double)pc[8 + k];
-            fprintf(stderr, "[bfs2 profile] wave-0 clock per root %.0f, per window %.0f:", tot / n_roots, tot / (double)(pc[0] ? pc[0] : 1));
-            for (int k = 0; k < 10; ++k) fprintf(stderr, " %s %.1f%%", names[k], 100.0 * (double)pc[8 + k] / (tot > 0 ? tot : 1));
-            fprintf(stderr, "\n");
-            const char *snames[7] = {"unseen list + adjacency ranges", "cstart zeros", "bucket bitmaps", "scans", "marks into LDS", "rank masks", "S list + bitmap restore"};
-            double stot = 0;
-            for (int k = 0; k < 7; ++k) stot += (double)pc[21 + k];
-            fprintf(stderr, "[bfs2 profile] father search, wave-0 clock per root %.0f:", stot / n_roots);
-            for (int k = 0; k < 7; ++k) fprintf(stderr, " %s %.1f%%", snames[k], 100.0 * (double)pc[21 + k] / (stot > 0 ? stot : 1));
-            fprintf(stderr, "\n");
-        }
-    }
-    if (e == hipSuccess && prof && v1) {
-        unsigned long long pc[16];
-        if (hipMemcpy(pc, a.prof, sizeof(pc), hipMemcpyDeviceToHost) == hipSuccess) {
-            const char *names[8] = {"nodes+scan", "batch form", "map+load+test", "empty chunk", "claim", "dup resolve", "compaction", "stores"};
-            double tot = 0;
-            for (int k = 0; k < 8; ++k) tot += (double)pc[k];
-            fprintf(stderr, "[bfs profile] %d roots, grid %d: batches %llu chunks %llu (empty %llu, with dups %llu); wave-0 shader-clock share:", n_items, grid, pc[8], pc[9], pc[10], pc[11]);
-            for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %.1f%%", names[k], 100.0 * (double)pc[k] / (tot > 0 ? tot : 1));
-            fprintf(stderr, "; cycles per chunk %.0f\n", tot / (double)(pc[9] ? pc[9] : 1));
-        }
-    }
     float ms = 0.f;
     if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_build_trees_device: %s", hipGetErrorString(e));
-    if (a.exp) fprintf(stderr, "[bfs experiment %d] kernel %.1f ms for %d roots (results invalid)\n", a.exp, ms, n_items);
-    GG_CHECK(ctx, stats[2] == 0 || (a.exp & ~(8 | 64 | 128)), GG_EINVAL, "gg_build_trees_device: a BFS reached a different number of nodes than the component sweep of the graph");
+    GG_CHECK(ctx, stats[2] == 0, GG_EINVAL, "gg_build_trees_device: a BFS reached a different number of nodes than the component sweep of the graph");
     ctx->ctr.bfs_kernel_ms += ms;
     ctx->ctr.bfs_trees += n_items;
     return GG_OK;
@@ -1779,7 +1635,6 @@ static int build_trees_lazy(gg_ctx *ctx, const int32_t *roots, int32_t n_roots) 
     a.lz_alloc = ctx->dev_ctr + 1508;
     a.lz_alloc_end = budget;
     a.scr_cap = (int)scr;
-    a.lz_ablate = getenv("GG_LZ_ABLATE") ? atoi(getenv("GG_LZ_ABLATE")) : 0;
     a.lz_easy = easy_levels;
     a.lz_limit_easy = (int)easy_cap;
     a.scr_order = ctx->lz_scratch.as<int32_t>();
@@ -1941,6 +1796,6 @@ extern "C" int gg_build_trees_device(gg_ctx *ctx, const int32_t *roots, int32_t 
     if (rc != GG_OK) return rc;
     ctx->tree_max_depth = stats[0];
     ctx->tree_max_list = stats[1];
-    ctx->t_edge_valid = (a.exp & ~(8 | 64 | 128)) == 0;
+    ctx->t_edge_valid = true;
     return GG_OK;
 }

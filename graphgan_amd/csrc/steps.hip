@@ -53,7 +53,6 @@ struct StepArgs {
     const int64_t *n_glob; // multi-GPU G step: pairs of ALL ranks in this step (device word) -> inv_n = 1 / *n_glob
     int is_d;
     int ppg;               // consecutive pairs handled by one 16-lane group
-    unsigned long long *prof;  // GG_DET_PROFILE: 100 MHz clock stamps of the small-batch kernel (wave 0 and the last wave), else null
     // STAGED (large fused batches on one replica, see path_count_kernel): stage row of the v-side gradient of pair p, and of
     // the u-side gradient of the run that ends at pair p (-2: no run ends there); -1 = hub row, atomics as before
     const int32_t *slot_v, *slot_u;
@@ -718,9 +717,6 @@ __global__ __launch_bounds__(DET_THREADS) void pair_grad_det_kernel(const StepAr
     const int t = threadIdx.x & 15, g = threadIdx.x >> 4;
     const int n = a.n, ld = a.ld, nchunk = ld >> 2;
     const float inv_n = a.n_glob ? 1.0f / (float)(*a.n_glob) : a.inv_n;
-    const bool stamp = a.prof && blockIdx.x == 0 && (threadIdx.x == 0 || threadIdx.x == DET_THREADS - 64);
-    unsigned long long *const pw = a.prof + (threadIdx.x ? 8 : 0);
-    if (stamp) pw[0] = wall_clock64();
     for (int s = threadIdx.x; s < 2 * n; s += DET_THREADS) ids[s] = s < n ? a.u[s] : a.v[s - n];
     for (int p = g; p < n; p += DET_GROUPS) {
         const int iu = a.u[p], iv = a.v[p];  // (the group's own pair: not through the LDS copy, which is for phase 2)
@@ -758,9 +754,7 @@ __global__ __launch_bounds__(DET_THREADS) void pair_grad_det_kernel(const StepAr
             coefb[p] = a.is_d ? ds + a.lambda * bv : ds;
         }
     }
-    if (stamp) pw[1] = wall_clock64();
     __syncthreads();
-    if (stamp) pw[2] = wall_clock64();
     // ---- phase 2: ONE WAVEFRONT per slot (wave w: slots w, w + 16, ...), everything about the slot wave-uniform (scalar code);
     // lane L owns the features L, L + 64, ...  The first slot that names a row owns it and adds the row's contributions in
     // ascending slot order, CB at a time (their LDS reads in flight together): the fp32 operation sequence per element is the
@@ -908,8 +902,13 @@ __global__ __launch_bounds__(DET_THREADS) void pair_grad_det_kernel(const StepAr
                         if (OPT == 1 && f < ld) { pm[k][i] = o.mE[ro + f]; pv[k][i] = o.vE[ro + f]; }
                     }
                     if (lane == 0) {
-                        pb[k][0] = o.b[r];
-                        if (OPT == 1) { pb[k][1] = o.mb[r]; pb[k][2] = o.vb[r]; }
+                        // (r is wave-uniform: left to the compiler these are scalar loads, copied to vector registers at once -- a
+                        // wait per slot, four round trips one after the other, lazy-Adam G step 12.8 -> 13.2 us.  From a vector
+                        // register the index gives vector loads that stay in flight with the moments'.)
+                        int rv = r;
+                        asm volatile("" : "+v"(rv));
+                        pb[k][0] = o.b[rv];
+                        if (OPT == 1) { pb[k][1] = o.mb[rv]; pb[k][2] = o.vb[rv]; }
                     }
                 }
             }
@@ -933,7 +932,6 @@ __global__ __launch_bounds__(DET_THREADS) void pair_grad_det_kernel(const StepAr
             if (leader_of(s, r, m)) own_row(s, r, m, false, none, none, none3);
         }
     }
-    if (stamp) pw[3] = wall_clock64();  // (one clock read per phase: s_memrealtime is itself a slow scalar memory operation -- a read per owner round measured itself)
 }
 
 // workgroups of the table-read-only variant: one round of slots (16 wavefronts) each, at most 8
@@ -1561,32 +1559,12 @@ int run_step(gg_ctx *ctx, int which, const int32_t *d_u, const int32_t *d_v, con
         const bool replicas = ctx->comm || ctx->fake_world > 1;
         const int fused = (!replicas && opt != GG_OPT_ADAM_DENSE && det_rows_fit_lds(ctx, s) && !getenv("GG_NO_FUSED_SMALL_STEP")) ? (opt == GG_OPT_SGD ? 2 : 1) : 0;
         const OptArgs o = make_opt_args(ctx, which);
-        static unsigned long long *det_prof = nullptr;
-        static const bool det_prof_on = getenv("GG_DET_PROFILE") != nullptr;
-        if (det_prof_on) {
-            if (!det_prof) GG_HIP(ctx, hipMalloc((void **)&det_prof, 16 * sizeof(unsigned long long)));
-            GG_HIP(ctx, hipMemsetAsync(det_prof, 0, 16 * sizeof(unsigned long long), ctx->stream));
-            s.prof = det_prof;
-        }
         hipError_t e;
         if (nfd <= 4) e = launch_pair_grad_det<4>(ctx, s, o, fused);
         else if (nfd <= 8) e = launch_pair_grad_det<8>(ctx, s, o, fused);
         else if (nfd <= 16) e = launch_pair_grad_det<16>(ctx, s, o, fused);
         else e = launch_pair_grad_det<32>(ctx, s, o, fused);
         GG_HIP(ctx, e);
-        if (det_prof_on) {  // debugging aid: one synchronisation per step; sums of the phase times per model, printed every 1 000 steps
-            static double acc_t[2][2][4] = {};
-            static long cnt[2] = {};
-            unsigned long long h[16];
-            GG_HIP(ctx, hipMemcpyAsync(h, det_prof, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-            GG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int w = 0; w < 2; ++w)
-                for (int k = 0; k < 3; ++k) acc_t[which][w][k] += h[8 * w + k + 1] > h[8 * w + k] ? 10.0 * (double)(h[8 * w + k + 1] - h[8 * w + k]) : 0.0;
-            if (++cnt[which] % 1000 == 0)
-                for (int w = 0; w < 2; ++w)
-                    fprintf(stderr, "[det] model %d n=%d wave %s: loads+coef %.0f ns, barrier %.0f, owners' sums + stores issued %.0f (means over %ld steps)\n", which, n, w ? "15" : "0",
-                            acc_t[which][w][0] / cnt[which], acc_t[which][w][1] / cnt[which], acc_t[which][w][2] / cnt[which], cnt[which]);
-        }
         if (fused) {
             GG_HIP(ctx, hipGetLastError());
             step_done(ctx, which, n);

@@ -104,7 +104,6 @@ struct WalkArgs {
     int32_t es_mode;         // 0 = off, 1 = a stale node is scored whole when the asking distribution needs most of it, 2 = always
     int32_t es_ratio, es_hub;
     int32_t *lv_fe;          // [total_walks] es index of the father candidate's score (gather tasks with a father entry)
-    int32_t exp;             // GG_WALK_EXPERIMENT: timing ablations (results are then WRONG): 1 / 2 = the weights kernel skips its big / small tasks, 64 / 32 = runs them twice (results stay right), 8 = per-level row counts
     // LAZY trees (gg_internal.h "LAZY trees", bfs_gpu.hip): slot r is exact through level L_r; the children list of a rank >= lzs_r
     // is resolved by the first walk that stands on it ("LAZY RESOLUTION" below) and appended to the slot's pool
     int32_t lazy;
@@ -449,7 +448,7 @@ __device__ __forceinline__ unsigned long long lazy_resolve_wave(const WalkArgs &
         if (e >= e1) return false;
         x = a.col[e];
         if (x == cur || lz_in(bits, x)) return false;
-        return !a.g_multi || (a.exp & 32768) || a.rev[a.rev[e]] == (int32_t)e;  // (exp 16384 / 32768 / 65536: timing ablations of the resolution -- no pair stage / no first-occurrence tests / no scans; results WRONG)
+        return !a.g_multi || a.rev[a.rev[e]] == (int32_t)e;
     };
     // candidates of the whole adjacency: what the list can hold at most -> its place in the pool
     int x0 = -1, ncand = 0;
@@ -479,12 +478,12 @@ __device__ __forceinline__ unsigned long long lazy_resolve_wave(const WalkArgs &
             unsigned long long kids;
             if (depth == 0) {
                 // a child unless a neighbour in V precedes cur
-                if (!(a.exp & 65536)) lz_flat_scan<0>(a, bits, bm, rk, ws, lane, (int)xq, (int)(xe - xq), my_rank, work);
+                lz_flat_scan<0>(a, bits, bm, rk, ws, lane, (int)xq, (int)(xe - xq), my_rank, work);
                 kids = m & ~ws->mask[0];
             } else {
                 // candidates that touch V are in cur's own level; the others are one level below cur
-                if (!(a.exp & 65536)) lz_flat_scan<1>(a, bits, bm, rk, ws, lane, (int)xq, (int)(xe - xq), 0, work);
-                const unsigned long long below_m = (a.exp & 16384) ? 0ull : m & ~ws->mask[0];
+                lz_flat_scan<1>(a, bits, bm, rk, ws, lane, (int)xq, (int)(xe - xq), 0, work);
+                const unsigned long long below_m = m & ~ws->mask[0];
                 wave_lds_sync();  // (every lane has read the mask)
                 ws->mask[0] = 0ull;
                 // their neighbours y (PAIRS (x, y), 64 at a time): is y in level L + 1, and with which key?
@@ -686,7 +685,6 @@ constexpr int CTR_ROWS = 200;   // ctr[CTR_ROWS + (block & 63)]: candidate rows 
 constexpr int CTR_HOPS_V = 264;  // ctr[CTR_HOPS_V + (block & 63)]: hop counts of the level pipeline, spread over 64 words
 constexpr int CTR_READS_V = 328; // (same-address atomics serialise at ~12 ns each); summed by the host
 constexpr int CTR_DISTS = 392;   // ctr[CTR_DISTS + (block & 63)]: (root, node) distributions set up by the level pipeline (owners), spread words
-constexpr int CTR_TINY = 456;    // (64 spare words)
 constexpr int CTR_GATHER = 520;  // ctr[CTR_GATHER + (block & 63)]: owner distributions that gather their scores from the edge-score cache, spread words
 constexpr int CTR_NODES = 584;   // ctr[CTR_NODES + (block & 63)]: nodes whose adjacency this launch scored into the cache, spread words
 constexpr int CTR_BASE = 648;    // ctr[CTR_BASE + level]: global chunk offset of the first PREFIX chunk of hop `level` (launch base + the prefix chunks
@@ -743,14 +741,14 @@ __device__ __forceinline__ void write_node_desc(int4 *desc, int64_t c, int cur, 
 // constants include the tree base and the Q3 row (no slot -> base hop), the level's prefix base is one word (written by the
 // previous score kernel) instead of a loop over the earlier levels' counters, the dedup is an LDS hash instead of a
 // backward scan (up to 255 dependent LDS reads for a hub root's walks), and the block's returning atomics go out from
-// three lanes at once instead of one after the other: 6-7 round trips.
+// separate lanes at once instead of one after the other: 6-7 round trips.
 __device__ __forceinline__ uint32_t dc_hash(unsigned long long key, uint32_t mask) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40) & mask; }
 
 // LAZY (trees exact through a level only, see "LAZY RESOLUTION"): on a level where a walk may stand on a node without a built
 // children list the kernel runs as two launches around the resolve kernel -- do_setup == 0: finish hop level-1 only, store the
 // walk state, claim the picked node's list if nobody has resolved it (the claimed walks go to lz_list); do_sample == 2: the
 // walk state is read back and hop `level` is set up as always, its children range taken from the node's pair.
-constexpr int CTR_LZ = 456;  // lc[CTR_LZ + level]: walks listed for the resolve kernel of `level` (the spare words of CTR_TINY)
+constexpr int CTR_LZ = 456;  // lc[CTR_LZ + level]: walks listed for the resolve kernel of `level` (the 64 words between CTR_DISTS and CTR_GATHER)
 template <bool LAZY>
 __global__ __launch_bounds__(256) void level_advance_kernel(const WalkArgs a, const int do_sample, const int do_setup, const int write_desc,
                                                             const int64_t cap_chunks) {
@@ -1128,10 +1126,10 @@ __global__ __launch_bounds__(256) void level_advance_kernel(const WalkArgs a, co
     const bool big = owns && k > BIG_TASK;
     const bool small = owns && p_chunks > 1 && !big;  // 16 < k <= BIG_TASK: a 16-lane group of the weights kernel (private single chunks are finished by the score kernel)
     // chunk offsets and task slots: in-wave exclusive scans, per-block totals through LDS, and the block's returning
-    // atomics issued by three lanes AT ONCE (a single word serves only ~88 returning atomics per us, and three of them one
-    // after the other were three round trips); the order of the blocks' regions in the buffers is irrelevant
-    __shared__ int wv_pch[4], wv_sch[4], wv_big[4], wv_own[4], wv_small[4], wv_gat[4], wv_node[4], wv_alive[4], wv_p24[4];
-    __shared__ unsigned long long blk_base[3];
+    // atomics issued by separate lanes AT ONCE (a single word serves only ~88 returning atomics per us, and one after the
+    // other they were a round trip each); the order of the blocks' regions in the buffers is irrelevant
+    __shared__ int wv_pch[4], wv_sch[4], wv_big[4], wv_own[4], wv_small[4], wv_gat[4], wv_node[4], wv_alive[4];
+    __shared__ unsigned long long blk_base[2];
     int inc_p = p_chunks, inc_s = s_chunks;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -1139,7 +1137,7 @@ __global__ __launch_bounds__(256) void level_advance_kernel(const WalkArgs a, co
         if (lane >= off) { inc_p += op; inc_s += os; }
     }
     const int wv = tid >> 6;
-    const unsigned long long big_bal = __ballot(big), small_bal = __ballot(small), p24_bal = __ballot(small && mode == 0 && p_chunks <= 4);
+    const unsigned long long big_bal = __ballot(big), small_bal = __ballot(small);
     const unsigned long long own_bal = __ballot(owns && mode != 1);  // tasks that read a current row: private owners + node scorings
     // distributions served from the cache: gather tasks of the weights kernel + walks that will gather themselves (counted per
     // walk: nothing dedups them; the walks behind a self-gathering owner are not counted)
@@ -1148,21 +1146,19 @@ __global__ __launch_bounds__(256) void level_advance_kernel(const WalkArgs a, co
     if (lane == 0) {
         wv_big[wv] = __popcll(big_bal); wv_small[wv] = __popcll(small_bal);
         wv_own[wv] = __popcll(own_bal); wv_gat[wv] = __popcll(gat_bal); wv_node[wv] = __popcll(node_bal); wv_alive[wv] = __popcll(alive_bal);
-        wv_p24[wv] = __popcll(p24_bal);
     }
     __syncthreads();
-    if (tid < 7) {
+    if (tid < 6) {
         auto tot = [&](const int *v) { return (unsigned long long)(v[0] + v[1] + v[2] + v[3]); };
         unsigned long long *word = nullptr;
         unsigned long long val = 0;
         if (tid == 0) { word = &a.lc[CTR_CHUNKS + a.level]; val = tot(wv_pch) | (tot(wv_sch) << 32); }
         else if (tid == 1) { word = &a.lc[CTR_BIG + a.level]; val = tot(wv_big) | (tot(wv_small) << 32); }
-        else if (tid == 2) { word = &a.lc[CTR_TINY + a.level]; val = ((a.exp & 16) && !LAZY) ? tot(wv_p24) : 0; }  // (GG_WALK_EXPERIMENT & 16: small tasks that score their own 17..64 candidates -- what a "finish in the score kernel" wave task would take off the weights kernel's list; the word is the resolve ticket of lazy launches)
-        else if (tid == 3) { word = &a.lc[CTR_DISTS + (blockIdx.x & 63)]; val = tot(wv_own); }
-        else if (tid == 4) { word = &a.lc[CTR_GATHER + (blockIdx.x & 63)]; val = tot(wv_gat); }
-        else if (tid == 5) { word = &a.lc[CTR_NODES + (blockIdx.x & 63)]; val = tot(wv_node); }
+        else if (tid == 2) { word = &a.lc[CTR_DISTS + (blockIdx.x & 63)]; val = tot(wv_own); }
+        else if (tid == 3) { word = &a.lc[CTR_GATHER + (blockIdx.x & 63)]; val = tot(wv_gat); }
+        else if (tid == 4) { word = &a.lc[CTR_NODES + (blockIdx.x & 63)]; val = tot(wv_node); }
         else { word = &a.lc[CTR_ALIVE + a.level]; val = tot(wv_alive); }  // walks still alive at this hop
-        if (tid < 3) blk_base[tid] = val ? atomicAdd(word, val) : 0ull;
+        if (tid < 2) blk_base[tid] = val ? atomicAdd(word, val) : 0ull;
         else if (val) atomicAdd(word, val);
     }
     __syncthreads();
@@ -1279,7 +1275,7 @@ __global__ __launch_bounds__(LZ_T) void lazy_resolve_kernel(const WalkArgs a) {
             const int found = s_n, n = min(found, LZ_LIST);
             if (n > 0) {
                 const int slot = a.slots[item];
-                if (LDS_BITS && !(a.exp & 8192)) {  // (GG_WALK_EXPERIMENT & 8192 / 4096: timing ablations -- no copy / no resolution; results are WRONG)
+                if (LDS_BITS) {
                     const uint2 *const src = a.lz_bm + (size_t)slot * a.lz_words;
                     for (int i0 = tid; i0 < a.lz_words; i0 += 8 * LZ_T) {  // (eight loads in flight per thread: one at a time this copy was 31 memory round trips per slot)
                         uint32_t wv[8];
@@ -1294,11 +1290,10 @@ __global__ __launch_bounds__(LZ_T) void lazy_resolve_kernel(const WalkArgs a) {
                 for (;;) {
                     const int i = __builtin_amdgcn_readfirstlane(atomicAdd(&s_next, lane == 0 ? 1 : 0));  // (a scalar: the loop branches on it; no lane-0 branch, see lazy_resolve_wave)
                     if (i >= n) break;
-                    if (a.exp & 4096) continue;
                     const int64_t w = w0 + s_list[i];
                     const int cur = __builtin_amdgcn_readfirstlane(a.st_cur[w]);
                     const int64_t deg = a.rowptr[cur + 1] - a.rowptr[cur];
-                    if (deg > a.lz_coop_min && deg <= 64 * LZ_COOP_CHUNKS && !(a.exp & 131072)) {  // (GG_WALK_EXPERIMENT & 131072: every list by one wavefront)
+                    if (deg > a.lz_coop_min && deg <= 64 * LZ_COOP_CHUNKS) {
                         const int j = __builtin_amdgcn_readfirstlane(atomicAdd(&s_nbig, lane == 0 ? 1 : 0));
                         s_big[j] = s_list[i];  // (every lane: the same word)
                     } else {
@@ -1426,7 +1421,6 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void level_score_kernel(const
     if (t == 0 && rows) atomicAdd(&blk_rows, rows);
     __syncthreads();
     if (threadIdx.x == 0 && blk_rows) atomicAdd(&a.lc[CTR_ROWS + (blockIdx.x & 63)], blk_rows);
-    if ((a.exp & 8) && threadIdx.x == 0 && blk_rows) atomicAdd(&a.lc[CTR_TINY + a.level], blk_rows);  // GG_WALK_EXPERIMENT & 8: rows per LEVEL (same-address atomics: a ~20 us tail)
 }
 
 // Where the scores of owner walk w's distribution are: its private score region, or (gather) the edge-score cache through
@@ -1597,11 +1591,9 @@ __global__ __launch_bounds__(256) void level_weights_kernel(const WalkArgs a, co
     const int64_t pch = (int64_t)(cw & 0xffffffffull), sch = (int64_t)(cw >> 32);
     if (sch > cap_chunks || pch == 0 || level_chunk_base(a) + pch > a.cap_total) return;
     if (blockIdx.x < BIG_BLOCKS) {
-        if (!(a.exp & 1)) weights_big_blocks(a);
-        if (a.exp & 64) { __syncthreads(); weights_big_blocks(a); }    // timing ablation: the class twice (idempotent, results stay right)
+        weights_big_blocks(a);
     } else {
-        if (!(a.exp & 2)) weights_small_blocks(a, (int)blockIdx.x - BIG_BLOCKS);
-        if (a.exp & 32) weights_small_blocks(a, (int)blockIdx.x - BIG_BLOCKS);
+        weights_small_blocks(a, (int)blockIdx.x - BIG_BLOCKS);
     }
 }
 
@@ -2152,10 +2144,6 @@ int launch_walk_sample(gg_ctx *ctx, int32_t n_slots, int64_t total_walks, int fo
     a.es_ratio = ctx->es_ratio_num;
     a.es_hub = ctx->es_hub;
     a.es_mode = 0;  // set below
-    {
-        static const int exp_env = getenv("GG_WALK_EXPERIMENT") ? atoi(getenv("GG_WALK_EXPERIMENT")) : 0;
-        a.exp = exp_env;
-    }
     a.w0 = 0;
     a.w_end = total_walks;
     a.lv_big_cap = total_walks;

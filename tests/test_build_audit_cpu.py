@@ -42,6 +42,83 @@ def test_scratch_check_accepts_the_build_and_rejects_a_spill(tmp_path, obj):
         assert res.returncode != 0 and "spills" in res.stderr
 
 
+ROOT = os.path.dirname(os.path.dirname(CSRC))
+# timing switches that made the shipped kernels compute wrong results; removed from the library (profiles/r19_switch_removal_*)
+REMOVED_SWITCHES = ("GG_WALK_EXPERIMENT", "GG_BFS_EXPERIMENT", "GG_BFS_PROFILE", "GG_LZ_ABLATE", "GG_K7_DBG", "GG_K7_ABLATIONS", "GG_DET_PROFILE")
+SOURCE_SUFFIXES = (".py", ".hip", ".cpp", ".c", ".h", ".sh", ".md", ".txt", ".json")
+
+
+def source_files(top):
+    """Text sources under `top` (a file, or a directory walked recursively); build products and caches are not sources."""
+    if os.path.isfile(top):
+        yield top
+        return
+    for dirpath, dirs, files in os.walk(top):
+        dirs[:] = [d for d in dirs if d != "__pycache__"]
+        for f in files:
+            if f.endswith(SOURCE_SUFFIXES) or f == "Makefile":
+                yield os.path.join(dirpath, f)
+
+
+def read(path):
+    return open(path, errors="replace").read()
+
+
+def test_removed_timing_switches_are_gone():
+    """None of the removed switches is named in the library, its header, the tools or the README."""
+    for top in ("graphgan_amd", "include", "tools", "README.md"):
+        for path in source_files(os.path.join(ROOT, top)):
+            text = read(path)
+            hits = [name for name in REMOVED_SWITCHES if name in text]
+            assert not hits, (path, hits)
+
+
+def readme_env_table():
+    """The rows of README's environment table ("| variable | effect |" up to the first line that is no row)."""
+    lines = read(os.path.join(ROOT, "README.md")).splitlines()
+    start = lines.index("| variable | effect |")
+    rows = []
+    for ln in lines[start:]:
+        if not ln.startswith("|"):
+            break
+        rows.append(ln)
+    return "\n".join(rows)
+
+
+def test_every_library_knob_is_in_the_readme_table():
+    """Every GG_... variable the library reads with getenv has its row (or row part) in README's environment table."""
+    names = set()
+    for path in source_files(CSRC):
+        names.update(re.findall(r'getenv\(\s*"(GG_[A-Z0-9_]+)"', read(path)))
+    assert len(names) > 40  # (the scan found the library's getenv calls)
+    table = readme_env_table()
+    documented = set(re.findall(r"`(GG_[A-Z0-9_]+)", table))
+    assert not sorted(names - documented), "read by the library, missing in README's environment table"
+
+
+def test_every_knob_a_test_sets_is_still_read():
+    """A GG_... variable that a test puts into the environment is read somewhere -- by the library, the package, bench.py or
+    the tests' own helpers: a kept knob must not leave with the removed ones (whose names only the test that proves them
+    inert still sets)."""
+    tests_dir = os.path.join(ROOT, "tests")
+    set_by_tests = set()
+    for f in sorted(os.listdir(tests_dir)):
+        if not f.endswith(".py"):
+            continue
+        text = read(os.path.join(tests_dir, f))
+        set_by_tests.update(re.findall(r'setenv\(\s*["\'](GG_[A-Z0-9_]+)["\']', text))
+        set_by_tests.update(re.findall(r'\[["\'](GG_[A-Z0-9_]+)["\']\]\s*=(?!=)', text))
+        set_by_tests.update(re.findall(r'["\'](GG_[A-Z0-9_]+)["\']\s*:', text))      # entries of an environment dict
+        set_by_tests.update(re.findall(r'environ,[^)]*?\b(GG_[A-Z0-9_]+)\s*=', text))  # keyword of a dict(os.environ, ...)
+    assert len(set_by_tests) > 20  # (the scan found the tests' settings)
+    read_somewhere = set()
+    reader = re.compile(r'(?:getenv\(|environ\.get\(|environ\[)\s*["\'](GG_[A-Z0-9_]+)["\']\]?(?!\s*=[^=])')
+    for top in ("graphgan_amd", "bench.py", "tests"):
+        for path in source_files(os.path.join(ROOT, top)):
+            read_somewhere.update(reader.findall(read(path)))
+    assert not sorted(set_by_tests - read_somewhere - set(REMOVED_SWITCHES)), "set by a test, read nowhere"
+
+
 def test_product_path_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under graphgan_amd/ may import, load or execute it (a product path that routed
     through the CPU restatement would void every parity claim), and bench.py may name it only inside its cpu_baseline legs."""
