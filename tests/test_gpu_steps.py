@@ -9,6 +9,7 @@ import pytest
 
 from oracle import graphgan_oracle as orc
 from tests.helpers import load_ca_grqc, load_small, ca_grqc_init_embeddings
+from tests.support import row_dot_shapes as rd
 
 pytestmark = pytest.mark.gpu
 
@@ -536,6 +537,106 @@ def test_fused_g_pass_embedding_widths(ga, d, monkeypatch):
     assert np.allclose(engs[0].get_embeddings(0), gen.E, rtol=2e-5, atol=2e-6)
     for e in engs:
         e.close()
+
+
+def _width_engine(ga, d, **kw):
+    """load_small(3) with tests/support/row_dot_shapes.py's table of width d for both models, whole trees of every root"""
+    g, n, graph = load_small(3)
+    E, b = rd.table(n, d)
+    eng = engine_with(ga, E, E, b, b, **kw)
+    rowptr, col = ga.graph_to_csr(n, graph)
+    eng.set_graph_csr(rowptr, col)
+    eng.build_trees(np.arange(n))
+    return n, rowptr, col, E, b, eng
+
+
+@pytest.mark.parametrize("d", rd.REWARD_WIDTHS)
+def test_prepare_g_rewards_at_every_row_width_instance(ga, d, monkeypatch):
+    """path_reward_kernel<1>, <2>, <4> (d = 6; 65, 128; 129) and the widths that decline it (257, 512: nch > 4 -- the pairs are
+    filled behind the walks and pair_reward_kernel runs on the device-side pair count): the pairs of a prepare_g behind a
+    prepare_d equal the pairs of the oracle's walks bit for bit, the rewards equal the numpy restatement to 1e-5 and the
+    per-pair kernel bit for bit."""
+    monkeypatch.delenv("GG_NO_PATH_REWARD", raising=False)
+    n, rowptr, col, E, b, eng = _width_engine(ga, d)
+    roots = slots = np.arange(n, dtype=np.int32)
+    off, nbr, base, dmax = orc.c_build_trees(n, rowptr, col, roots)
+    Ep = orc.pad_rows(E)
+    deg = (rowptr[1:] - rowptr[:-1]).astype(np.int32)
+    want = orc.c_walk_sample(Ep, b, off, nbr, base, roots, slots, deg, True, 9, 0, dmax + 3)  # (removes father entries: Q3)
+    _, _, _, st = eng.prepare_d(slots, 9, 0)
+    assert np.array_equal(st, want["root_status"])
+    want = orc.c_walk_sample(Ep, b, off, nbr, base, roots, slots, np.full(n, 20, np.int32), False, 9, 1, dmax + 3)
+    n1, n2 = [], []
+    for wlk in range(n * 20):
+        L = want["path_len"][wlk]
+        if L > 0:
+            for a, c in orc.pairs_from_path(list(want["paths"][wlk, :L]), 2):
+                n1.append(a)
+                n2.append(c)
+    g1, g2, rew, st = eng.prepare_g(slots, 20, 9, 1)
+    assert np.array_equal(st, want["root_status"])
+    assert len(n1) > 5000 and np.array_equal(g1, np.array(n1, np.int32)) and np.array_equal(g2, np.array(n2, np.int32))
+    dis = orc.Discriminator(E, 1e-3)
+    dis.b[:] = b
+    err = np.max(np.abs(rew - dis.reward(g1.astype(np.int64), g2.astype(np.int64))))
+    print("d = %3d: %d pairs, |reward - numpy| %.3g" % (d, len(g1), err))
+    assert err <= 1e-5
+    assert np.array_equal(eng.pair_reward(g1, g2).view(np.uint32), rew.view(np.uint32))
+    if rd.path_reward_taken(d, 2):
+        assert rd.path_reward_instance(d) == rd.instance_of(d) and not rd.wide(d)
+        monkeypatch.setenv("GG_NO_PATH_REWARD", "1")
+        h1, h2, rew_pairs, _ = eng.prepare_g(slots, 20, 9, 1)
+        monkeypatch.delenv("GG_NO_PATH_REWARD")
+        assert np.array_equal(h1, g1) and np.array_equal(h2, g2)
+        assert np.array_equal(rew_pairs.view(np.uint32), rew.view(np.uint32))
+    else:
+        assert rd.nch_of(d) > 4 and rd.wide(d)  # these widths take the per-pair kernel by themselves
+    eng.close()
+
+
+PASS_LR_GEN = 0.05  # the generator's loss is a MEAN over ~14 000 pairs: at 1e-3 no entry of its table would move by 1e-4
+
+
+@pytest.mark.parametrize("d", rd.PASS_WIDTHS)
+def test_prepared_passes_on_both_sides_of_ld_256(ga, d):
+    """prepare_d, a fused d_pass, prepare_g, a fused g_pass at d = 256 -- the last width at which the staged gradient, the
+    whole-walk generator pass and the whole-walk reward are taken -- and at 260 and 512, where all three are declined.  SGD, so
+    that the comparison is linear in the gradient (test_fused_d_pass_wide_rows_keep_every_column): both tables and both biases
+    against the float64 np.add.at restatement of one SGD step on the prepared rows and pairs, and the columns from 256 on must
+    have moved."""
+    n, rowptr, col, E, b, eng = _width_engine(ga, d, optimizer=ga.GG_OPT_SGD, lr_gen=PASS_LR_GEN)
+    slots = np.arange(n, dtype=np.int32)
+
+    def sgd(model, lr, u, v, x):
+        _, gu, gv, gb = model.loss_and_grads(u.astype(np.int64), v.astype(np.int64), x, 1e-5)
+        GE, Gb = np.zeros_like(model.E, dtype=np.float64), np.zeros(n)
+        np.add.at(GE, u, gu)
+        np.add.at(GE, v, gv)
+        np.add.at(Gb, v, gb)
+        return E - (lr * GE).astype(np.float32), b - (lr * Gb).astype(np.float32)
+
+    for which, lr in ((1, 1e-3), (0, PASS_LR_GEN)):
+        if which == 1:
+            u, v, x, _ = eng.prepare_d(slots, 9, 0)
+            eng.d_pass([0], len(u))
+            model = orc.Discriminator(E, lr)
+        else:
+            u, v, x, _ = eng.prepare_g(slots, 20, 9, 1)  # (the rewards of the updated discriminator)
+            eng.g_pass([0], len(u))
+            model = orc.Generator(E, lr)
+        model.b[:] = b
+        assert len(u) > (400 if which == 1 else 10000)
+        want_E, want_b = sgd(model, lr, u, v, x)
+        got_E, got_b = eng.get_embeddings(which), eng.get_bias(which)
+        moved = np.abs(got_E - E)
+        print("d = %3d model %d: %d rows, moved %.3g (columns >= 256: %.3g), |dE| %.3g |db| %.3g" %
+              (d, which, len(u), moved.max(), moved[:, 256:].max(initial=0.0), np.abs(got_E - want_E).max(), np.abs(got_b - want_b).max()))
+        assert moved.max() > 1e-4
+        if rd.wide(d):
+            assert moved[:, 256:].max() > 1e-4
+        assert np.allclose(got_E, want_E, rtol=2e-5, atol=1e-6), which
+        assert np.allclose(got_b, want_b, rtol=2e-5, atol=1e-6), which
+    eng.close()
 
 
 def test_empty_draw_resets_the_resident_rows(ga):

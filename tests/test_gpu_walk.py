@@ -89,6 +89,9 @@ def test_small_graphs_bit_exact(ga, gi, walk_mode):
 
 @pytest.mark.parametrize("d", [4, 50, 128, 200, 256])
 def test_embedding_widths(ga, d):
+    """A few row widths in the DEFAULT mode only (the level pipeline to the end: level_score_kernel<1>, <2> and <4>; the
+    finisher scores nothing here).  The width x mode matrix -- every template instance of the row dot up to d = 512 in the
+    modes that make each kernel score hops, on whole and on lazy trees -- is tests/test_gpu_walk_widths.py."""
     g, n, graph = load_small(1)
     rs = np.random.RandomState(d)
     E = (rs.randn(n, d) * (1.5 / np.sqrt(d))).astype(np.float32)
