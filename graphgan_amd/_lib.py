@@ -29,6 +29,7 @@ GG_OK, GG_EINVAL, GG_ECAPACITY, GG_EHIP, GG_ECOMM, GG_ENOMEM, GG_EIO = 0, -1, -2
 GG_OPT_ADAM_DENSE, GG_OPT_ADAM_LAZY, GG_OPT_SGD = 0, 1, 2
 GG_ROOT_OK, GG_ROOT_ABORTED, GG_ROOT_EMPTY = 0, 1, 2
 GG_GS_FOR_D, GG_GS_Q3_STORE = 1, 2
+GRAM_MAX_GRID = 512  # == GRAM_MAX_GRID of csrc/gram.hip: workgroups of a gg_gram sweep at most (its grid is min(this, ceil(m / 64)))
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
                GG_ENOMEM: "GG_ENOMEM", GG_EIO: "GG_EIO"}
 
@@ -132,6 +133,7 @@ SIGNATURES = {
     "gg_kmeans_step": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gg_kmeans_fit": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gg_silhouette": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _i64, ctypes.c_int, _P, _i64, ctypes.c_int, _P, _P, _P, _P, _P, _P]),
+    "gg_gram": (ctypes.c_int, [_P, ctypes.c_int, _P, _i64, _P, _P, _P, _P]),
     "gg_get_embeddings": (ctypes.c_int, [_P, _i32, _P]),
     "gg_get_bias": (ctypes.c_int, [_P, _i32, _P]),
     "gg_write_embeddings": (ctypes.c_int, [_P, _i32, ctypes.c_char_p, _i32]),

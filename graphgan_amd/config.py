@@ -108,6 +108,12 @@ engine_cluster_max_iters = 100  # Lloyd sweeps of a restart at most
 engine_cluster_silhouette = False
 engine_sil_precision = "fp32"   # distances from exact "fp32" scores or "bf16" (the silhouette of the bf16-rounded table)
 engine_sil_max_rows = 0         # 0 = every row; else a sample of that many rows (RandomState([engine_seed, 0x5349])) against all columns
+# spectrum of the embedding rows (evaluation/embedding_spectrum.py): with engine_emb_spectrum = True evaluation() appends, under any
+# app, after the *_sil lines and before gen_nll, "gen_spec:erank= pr= top1= top10= var= mean_norm= n= d=" and "dis_spec:..." -- the
+# effective rank, participation ratio and leading shares of the covariance spectrum of the rows of the nodes with a training edge,
+# their total variance and the norm of their mean (two gg_gram sweeps on the device, eigh on the host).  Needs no file beyond the
+# training edges: no labels, no test edges, no negatives.
+engine_emb_spectrum = False
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

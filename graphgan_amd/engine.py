@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import GGConfig, GGCounters, check, lib
+from .evaluation.embedding_spectrum import pca_cov, pca_eig
 
 
 def _ptr(a):
@@ -980,6 +981,70 @@ class Engine:
         self._ck(lib.gg_silhouette(self._ctx, which, _ptr(nodes_a), _ptr(assign_a), m, k, _ptr(rows_a), n_out if rows_a is not None else 0,
                                    {"fp32": 0, "bf16": 1}[precision], _ptr(sil), _ptr(a), _ptr(b), _ptr(nearest), _ptr(mean), ctypes.byref(ms)))
         return dict(sil=sil, a=a, b=b, nearest=nearest, mean=float(mean[0]), ms=ms.value)
+
+    # ------------------------------------------------------------------ PCA of the rows (gg_gram)
+    def gram(self, nodes, center=None, which=0, gram=True):
+        """The centred Gram matrix of the rows ``nodes`` of table ``which`` (gg_gram): with c_i = E[node_i] - center in fp32
+        (``center``: floats [n_emb], None = no subtraction) ``sums`` = sum_i c_i and ``gram`` = sum_i c_i c_i^T, fp32 chains per
+        workgroup on the matrix cores, added in float64.  ``gram=False`` is the sums-only sweep (the mean pass; the same ``sums``
+        bits).  Returns dict(sums float64 [n_emb], gram float64 [n_emb, n_emb] or None, ms)."""
+        fn = "gram"
+        nodes_a = self._km_args(fn, nodes, which)
+        cen = None
+        if center is not None:
+            cen = np.ascontiguousarray(center, dtype=np.float32)
+            if cen.shape != (self.n_emb,) or not np.all(np.isfinite(cen)):
+                raise ValueError("%s: center must be %d finite floats, got shape %r" % (fn, self.n_emb, cen.shape))
+        d = self.n_emb
+        sums = np.zeros(d, dtype=np.float64)
+        G = np.zeros((d, d), dtype=np.float64) if gram else None
+        ms = ctypes.c_double()
+        self._ck(lib.gg_gram(self._ctx, which, _ptr(nodes_a), len(nodes_a), _ptr(cen), _ptr(sums), _ptr(G), ctypes.byref(ms)))
+        return dict(sums=sums, gram=G, ms=ms.value)
+
+    def pca(self, nodes, n_components=None, which=0):
+        """PCA of the rows ``nodes`` (m >= 2) of table ``which`` in two sweeps on the device.  Pass A, ``gram(center=None,
+        gram=False)``: mean64 = sums / m, center = float32(mean64).  Pass B, ``gram(center)``: G and the residual sums r (the fp32
+        centre is not the float64 mean).  Host, float64: cov = (G - outer(r, r) / m) / m, numpy.linalg.eigh, eigenvalues
+        descending and clipped at 0, every eigenvector signed so that its largest-magnitude entry (the lowest index on ties) is
+        positive.  Returns dict(mean fp32 [d], eigenvalues float64 [d], components fp32 [n_components, d] (rows; None = all d),
+        cov float64 [d, d], m, mean64 -- pass A's float64 mean --, ms -- the device time of both sweeps)."""
+        fn = "pca"
+        nodes_a = self._km_args(fn, nodes, which)
+        m, d = len(nodes_a), self.n_emb
+        if m < 2:
+            raise ValueError("%s: needs m >= 2 rows, got %d" % (fn, m))
+        if n_components is None:
+            n_components = d
+        if isinstance(n_components, bool) or not isinstance(n_components, (int, np.integer)) or not 1 <= int(n_components) <= d:
+            raise ValueError("%s: n_components must be an integer in [1, %d], got %r" % (fn, d, n_components))
+        a = self.gram(nodes_a, center=None, which=which, gram=False)
+        mean64 = a["sums"] / m
+        center = mean64.astype(np.float32)
+        b = self.gram(nodes_a, center=center, which=which, gram=True)
+        cov = pca_cov(b["gram"], b["sums"], m)
+        lam, vec = pca_eig(cov)
+        return dict(mean=center, eigenvalues=lam, components=np.ascontiguousarray(vec[:int(n_components)], dtype=np.float32), cov=cov, m=m,
+                    mean64=mean64, ms=a["ms"] + b["ms"])
+
+    def pca_transform(self, nodes, mean, components, which=0):
+        """The rows ``nodes`` of table ``which`` projected on ``components`` [n_components <= 128, n_emb] about ``mean`` [n_emb]
+        -> fp32 [m, n_components].  It is the logits of ``classifier_predict`` with W = components and
+        b = float32(-(components64 @ mean64)): the dot products run on the uncentred rows, so the rounding is relative to
+        |W| |x|, not to the centred value -- good for plotting and for features, not a bit contract of its own."""
+        fn = "pca_transform"
+        W = np.ascontiguousarray(components, dtype=np.float32)
+        mu = np.ascontiguousarray(mean, dtype=np.float32)
+        if W.ndim != 2 or W.shape[1] != self.n_emb or mu.shape != (self.n_emb,):
+            raise ValueError("%s: components must be [n_components, %d] and mean [%d], got %r and %r" % (fn, self.n_emb, self.n_emb, W.shape, mu.shape))
+        if not 1 <= W.shape[0] <= 128:
+            raise ValueError("%s: n_components = %d outside [1, 128]" % (fn, W.shape[0]))
+        nodes_a = self._km_args(fn, nodes, which)
+        bias = (-(W.astype(np.float64) @ mu.astype(np.float64))).astype(np.float32)
+        if W.shape[0] == 1:  # (gg_classifier_predict takes 2 .. 128 classes: a second, zero component rides along)
+            z = self.classifier_predict(nodes_a, np.vstack([W, np.zeros_like(W)]), np.append(bias, np.float32(0)), which=which, logits=True)[1]
+            return np.ascontiguousarray(z[:, :1])
+        return self.classifier_predict(nodes_a, W, bias, which=which, logits=True)[1]
 
     def get_embeddings(self, which):
         """sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = gen, 1 = dis."""

@@ -50,6 +50,7 @@ from graphgan_amd.evaluation import recommendation as rec  # noqa: E402
 from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
 from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
 from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
+from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -95,6 +96,18 @@ def _check_node_clustering(cfg):
         raise ValueError("engine_node_clustering needs labels: config.labels_filename does not exist (%r)" % (path,))
 
 
+def _check_emb_spectrum(cfg):
+    """the spectrum lines need two nodes with a training edge, under any app (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_emb_spectrum", False):
+        return
+    path = getattr(cfg, "train_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_emb_spectrum needs the training edges: config.train_filename does not exist (%r)" % (path,))
+    n = len(espec.trained_nodes(path))
+    if n < 2:
+        raise ValueError("engine_emb_spectrum needs at least two nodes with a training edge: %r has %d" % (path, n))
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
@@ -105,6 +118,7 @@ class GraphGAN(object):
         _check_lp_classifier(cfg)
         _check_link_rank(cfg)
         _check_node_clustering(cfg)
+        _check_emb_spectrum(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -483,6 +497,7 @@ class GraphGAN(object):
         _check_lp_classifier(cfg)
         _check_link_rank(cfg)
         _check_node_clustering(cfg)
+        _check_emb_spectrum(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -555,6 +570,13 @@ class GraphGAN(object):
                                                   max_rows=int(_cfg(cfg, "engine_sil_max_rows", 0)), seed=self.seed)
                     fit = fits[i]
                     results.append(nsil.format_results(cfg.modes[i], nse.eval_node_silhouette(fit["nodes"], fit["classes"], fit["assign"], fit["k"])))
+        if _cfg(cfg, "engine_emb_spectrum", False):
+            # spectrum of the covariance of the rows of the nodes with a training edge (two gg_gram sweeps, eigh on the host): one
+            # line per mode, "gen_spec:erank=<e> pr=<p> top1=<t> top10=<t> var=<v> mean_norm=<n> n=<n> d=<d>" (without an engine: the
+            # same two passes in float64 on the .emb text); no labels, test edges or negatives are read
+            for i in range(2):
+                ese = espec.EmbeddingSpectrumEval(cfg.emb_filenames[i], cfg.train_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i)
+                results.append(espec.format_results(cfg.modes[i], ese.eval_embedding_spectrum()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

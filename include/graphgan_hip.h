@@ -601,6 +601,28 @@ int gg_silhouette(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *a
                   float *sil_out, float *a_out, float *b_out, int32_t *nearest_out /* each [n_rows or m] or NULL */,
                   double *mean_out /* [1] or NULL */, double *ms_out);
 
+/* ---- centred Gram matrix of gathered rows (additive entry point; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour
+ * changes).  The device part of the PCA of the FROZEN rows x_i = E[nodes[i]] of table `which` (0 = generator, 1 = discriminator):
+ * nothing of size m x n_emb crosses to the host.  With d = n_emb, rows i = 0 .. m - 1:
+ *   c_ij        = x_ij - center[j], ONE fp32 subtraction; center == NULL: c = x bit for bit (a NULL centre and an all-(+0) centre
+ *                 give the same bits).  Rows behind m and columns behind d contribute exact zeros, never 0 - center.
+ *   grid        = min(512, ceil(m / 64)) persistent workgroups over 64-row tiles, round robin (tile t belongs to workgroup
+ *                 t mod grid): a function of m alone.
+ *   part_w[j][l] = the k-ordered fmaf chain from 0.0 of c_ij c_il over the rows of workgroup w in ascending order (the arithmetic
+ *                 of v_mfma_f32_32x32x2_f32);   psum_w[j] = the fp32 chain s = s + c_ij over the same rows.
+ *   symmetry    only the tiles (a, b), a <= b, of the 32 x 32 output tiling are computed; the mirror is a copy:
+ *                 gram[j][l] == gram[l][j] bit for bit.
+ *   gram_out[j][l] = sum_w (double)part_w[j][l],   sums_out[j] = sum_w (double)psum_w[j]: float64, w ascending, by a second kernel.
+ * gram_out == NULL takes a sums-only sweep (the mean pass: gather, subtract, add; no product), with the same sums bits.
+ * Every output may be NULL.  ms_out: HIP-event time of the device work (sweep and reduction).
+ * limits       n_emb <= 256, 1 <= m <= 2^31 - 1, node ids in [0, n_node), free to repeat, center finite.  Anything else:
+ *              GG_EINVAL, the gg_last_error text names the entry point and the offending entry, nothing is launched.
+ * determinism  no floating-point atomics: the same inputs and table give the same bits.
+ * memory       the stage is grid x d x d floats (134 MB at 512 workgroups and d = 256); temporary device buffers are freed on
+ *              every exit path. */
+int gg_gram(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, const float *center /* [d] or NULL */,
+            double *sums_out /* [d] or NULL */, double *gram_out /* [d * d] row-major or NULL */, double *ms_out);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
