@@ -115,6 +115,7 @@ SIGNATURES = {
     "gg_all_score": (ctypes.c_int, [_P, _P, _i32, _P]),
     "gg_all_score_reduce": (ctypes.c_int, [_P, _P, _i32, _i32, _i32, _P, _P, _P, _P]),
     "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "gg_topk_metric": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _i64, _P, _P, _P]),
     "gg_rank_scores": (ctypes.c_int, [_P, _i32, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),

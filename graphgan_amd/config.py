@@ -114,6 +114,15 @@ engine_sil_max_rows = 0         # 0 = every row; else a sample of that many rows
 # their total variance and the norm of their mean (two gg_gram sweeps on the device, eigh on the host).  Needs no file beyond the
 # training edges: no labels, no test edges, no negatives.
 engine_emb_spectrum = False
+# k-NN node classification (evaluation/node_knn.py): with engine_nc_knn = True evaluation() appends, under any app, after the *_spec
+# lines and before gen_nll, "gen_knn:acc= macro_f1= k= metric= n_train= n_test=" and "dis_knn:..." -- every test node of the
+# classifier's split (engine_nc_train_ratio, engine_seed) takes the majority label of its k nearest TRAINING nodes, found by one
+# streamed top-K over that candidate set on the device (gg_topk_metric).  No optimiser, nothing to tune but k and the metric.
+# Needs labels_filename (lines of "node label"); k may not exceed the number of training nodes.
+engine_nc_knn = False
+engine_knn_k = 10               # neighbours that vote, 1 .. 256
+engine_knn_metric = "cosine"    # "cosine" | "l2" | "dot"
+engine_knn_precision = "fp32"   # neighbour scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

@@ -125,6 +125,30 @@ __device__ __forceinline__ void bf16_score_tiles(const uint4 *Eb, const int32_t 
     }
 }
 
+// |x|^2 as the stream computes x . x in fp32: the k-ordered fmaf chain from 0.0 -- over the bf16-rounded row when BF.  Row p of the
+// output is table row src[p] (src == NULL: row p itself); src[p] < 0 gives 0.  Shared by the silhouette (silhouette.hip: the rows
+// of its cluster-sorted copy; the kernel keeps the name of this first user, which the build's audit counts) and the metric top-K
+// (topk_score.hip: every table row).
+template <bool BF>
+__global__ __launch_bounds__(256) void sil_norm_kernel(const float *E, int ld, const int32_t *src, int n_rows, float *h) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_rows) return;
+    const int node = src ? src[p] : p;
+    float acc = 0.f;
+    if (node >= 0) {
+        const float *x = E + (int64_t)node * ld;
+        for (int kk = 0; kk < ld; kk += 4) {
+            float4 v = *(const float4 *)(x + kk);
+            if (BF) { v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w; }
+            acc = __builtin_fmaf(v.x, v.x, acc);
+            acc = __builtin_fmaf(v.y, v.y, acc);
+            acc = __builtin_fmaf(v.z, v.z, acc);
+            acc = __builtin_fmaf(v.w, v.w, acc);
+        }
+    }
+    h[p] = acc;
+}
+
 // ---- host plan shared by gg_all_score, gg_all_score_reduce and gg_topk_scores (all_score.hip) ----
 
 // every rows[i] in [0, n_node), or GG_EINVAL "<entry>: row id .. out of range" (rows == NULL: all rows, nothing to check)

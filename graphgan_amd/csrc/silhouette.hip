@@ -48,27 +48,6 @@ struct SilArgs {
     int chunk;
 };
 
-// |x|^2 as the stream computes x . x in fp32: the k-ordered fmaf chain from 0.0 -- over the bf16-rounded row when BF
-template <bool BF>
-__global__ __launch_bounds__(256) void sil_norm_kernel(const float *E, int ld, const int32_t *src, int n_rows, float *h) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_rows) return;
-    const int node = src[p];
-    float acc = 0.f;
-    if (node >= 0) {
-        const float *x = E + (int64_t)node * ld;
-        for (int kk = 0; kk < ld; kk += 4) {
-            float4 v = *(const float4 *)(x + kk);
-            if (BF) { v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w; }
-            acc = __builtin_fmaf(v.x, v.x, acc);
-            acc = __builtin_fmaf(v.y, v.y, acc);
-            acc = __builtin_fmaf(v.z, v.z, acc);
-            acc = __builtin_fmaf(v.w, v.w, acc);
-        }
-    }
-    h[p] = acc;
-}
-
 // the fp32 copy [n_rows, ld]: row p = E[src[p]], zeros where src[p] < 0
 __global__ __launch_bounds__(256) void sil_gather_kernel(const float *E, int ld, const int32_t *src, int64_t n_quads, float *X) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -18,6 +18,8 @@
 // in place; the new K-th key becomes the row's tau.  A wavefront's columns only grow, so a candidate never ties a list entry.
 // topk_merge_kernel then merges the (split, wavefront) lists of a row on the device (one workgroup per row, rank merge in LDS,
 // a list whose head does not beat the running K-th key is skipped).
+// gg_topk_metric (cosine / squared Euclidean order, a candidate set, exclude = 2) runs the same kernels as further template
+// instances: see ListConsumer.
 // The tiles come from the producers K7's streamed consumer uses (score_tiles.h):
 //   fp32: f32_score_tiles -- the k-ordered fmaf chain from 0.0, so the scores are bit-identical to gg_all_score (zero bias)
 //         and the oracle's rows;
@@ -48,7 +50,15 @@ struct TopkOut {
     const int32_t *adj;
     u64 *part;                // [n_rows][n_sub][k] keys, descending, 0 = empty
     int n_sub;                // 4 per column split
+    // gg_topk_metric only (the instances of gg_topk_scores read none of these):
+    const float *colv;        // [n_node] the column's scalar: w_c = 1 / sqrt(h_c) (cosine), h_c = |x_c|^2 (l2)
+    const uint32_t *member;   // [ceil(n_node / 32)] bit c: column c is a candidate (instances with a bitmap)
+    int not_self;             // exclude = 2: column u is not eligible in row u (instances with a bitmap)
 };
+
+// The ordering value t of a score s under the metric (include/graphgan_hip.h, gg_topk_metric): one fp32 operation with the
+// column's scalar.  Lists, tau and keys hold t; topk_merge_kernel maps t to the reported value with the row's scalar.
+enum { TK_DOT = 0, TK_COS = 1, TK_L2 = 2 };
 
 __device__ __forceinline__ u64 topk_key(float x, int col) {
     uint32_t u = __float_as_uint(x);
@@ -153,7 +163,10 @@ __device__ __forceinline__ void lists_init(WaveLists &st, const TopkOut &o, int 
     }
 }
 
-// One finished 32 x 32 tile of the wavefront: lane holds column `col` (valid iff ok) of 16 rows.
+// One finished 32 x 32 tile of the wavefront: lane holds column `col` (valid iff ok) of 16 rows; acc holds the ordering values.
+// CAND: the membership bit of the column (and exclude = 2's "not the row's own node") is tested where the adjacency is: on the
+// insertion path only, so an ineligible column never enters a list and never raises tau.
+template <bool CAND>
 __device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, int r0, int sub, const f32x16 &acc, int col, bool ok) {
     bool any = false;
 #pragma unroll
@@ -176,6 +189,7 @@ __device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, i
             if (((pm >> (32 * h)) & 0xffffffffull) == 0) continue;
             const int row = r0 + tile_row(reg, h);
             bool cand = p && hi == h;
+            if (CAND && cand) cand = ((o.member[col >> 5] >> (col & 31)) & 1u) != 0 && !(o.not_self && col == o.rows[row]);
             if (cand && o.adj) {
                 const int u = o.rows[row];
                 const int64_t b = o.adj_ptr[u], e = o.adj_ptr[u + 1];
@@ -192,6 +206,11 @@ __device__ __forceinline__ void lists_consume(WaveLists &st, const TopkOut &o, i
 // The consumer handed to the producers of score_tiles.h: the wavefront's lists of the tile's rows; scores carry no bias.
 // init() (the lists' global stores) runs BEHIND the staging of the requested rows: in front of it, the exclusion test's loads of
 // o.rows / o.adj_ptr stopped being scalar loads and fp32 with exclude = 1 ran 4 % slower.
+// METRIC / CAND: the instance <TK_DOT, false> is gg_topk_scores' consumer -- no scalar load, no bitmap, the scores themselves.
+// Under a metric the lane loads ITS column's scalar once per tile (one coalesced 4-byte load per lane) and turns its 16 scores
+// into ordering values with one multiply (cosine: s * w_c) or one fmaf (l2: s - h_c / 2) each; everything behind that -- the
+// 16 compares with tau, the ballot, the insertion path -- runs on the ordering values unchanged.
+template <int METRIC, bool CAND>
 struct ListConsumer {
     WaveLists st;
     const TopkOut &o;
@@ -199,26 +218,45 @@ struct ListConsumer {
     __device__ __forceinline__ ListConsumer(const TopkOut &o_, int r0_, int sub_) : o(o_), r0(r0_), sub(sub_) {}
     __device__ __forceinline__ void init() { lists_init(st, o, r0, sub); }
     __device__ __forceinline__ float start(int, bool) const { return 0.f; }
-    __device__ __forceinline__ void operator()(const f32x16 &acc, int col, bool ok) { lists_consume(st, o, r0, sub, acc, col, ok); }
-    __device__ __forceinline__ void operator()(const f32x16 (&acc)[1], int col, bool ok) { lists_consume(st, o, r0, sub, acc[0], col, ok); }
+    __device__ __forceinline__ void operator()(const f32x16 &acc, int col, bool ok) {
+        if (METRIC == TK_DOT) {
+            lists_consume<CAND>(st, o, r0, sub, acc, col, ok);
+        } else {
+            const float cv = ok ? o.colv[col] : 0.f;  // (columns behind the split's end: never a candidate)
+            f32x16 t;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) t[reg] = METRIC == TK_COS ? acc[reg] * cv : __builtin_fmaf(-0.5f, cv, acc[reg]);
+            lists_consume<CAND>(st, o, r0, sub, t, col, ok);
+        }
+    }
+    __device__ __forceinline__ void operator()(const f32x16 (&acc)[1], int col, bool ok) { (*this)(acc[0], col, ok); }
 };
 
+template <int METRIC, bool CAND>
 __global__ __launch_bounds__(256) void topk_f32_kernel(const float *E, int n_node, int ld, int cols_per_split, TopkOut o) {
     extern __shared__ float As_all[];  // [32][ld + 1]: the tile's 32 requested rows, staged once
     __shared__ float Bs[128][ST_KC + 1];
     const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + (threadIdx.x >> 6);
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    ListConsumer lists(o, r0, sub);
+    ListConsumer<METRIC, CAND> lists(o, r0, sub);
     f32_score_tiles(E, ld, o.rows, o.n_rows, r0, cbeg, cend, As_all, Bs, lists);
 }
 
 // KS k-steps of 16; the next tile's B fragments are prefetched while they fit (KS <= 16).
-template <int KS>
+template <int KS, int METRIC, bool CAND>
 __global__ __launch_bounds__(256) void topk_bf16_kernel(const uint4 *Eb, int n_node, int cols_per_split, TopkOut o) {
     const int split = blockIdx.x, r0 = blockIdx.y * 32, sub = 4 * split + (threadIdx.x >> 6);
     const int cbeg = split * cols_per_split, cend = min(n_node, cbeg + cols_per_split);
-    ListConsumer lists(o, r0, sub);
+    ListConsumer<METRIC, CAND> lists(o, r0, sub);
     bf16_score_tiles<KS, 1, (KS <= 16)>(Eb, o.rows, o.n_rows, r0, cbeg, cend, lists);
+}
+
+// In place: h_c = |x_c|^2 -> w_c = 1 / sqrt(h_c), a correctly rounded square root and one IEEE division; 0 where h_c == 0
+__global__ __launch_bounds__(256) void topk_rsqrt_kernel(float *v, int n) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const float h = v[p];
+    v[p] = h == 0.f ? 0.f : 1.0f / __builtin_sqrtf(h);
 }
 
 // Count of keys > x in a descending list of k keys.
@@ -234,7 +272,11 @@ __device__ __forceinline__ int count_above(const u64 *L, int k, u64 x) {
 
 // One workgroup per requested row: the row's n_sub lists merged into one k-list in LDS (rank merge: an entry's new position is
 // its index plus the entries of the other list above it; keys are distinct), written out as (column, score), -1 / -inf padded.
-__global__ __launch_bounds__(256) void topk_merge_kernel(const u64 *part, int n_sub, int k, int32_t *out_col, float *out_score) {
+// Under a metric the keys hold the ordering value t; the reported value is one more fp32 operation with the ROW's scalar
+// rowv[rows[row]]: t * w_u (cosine), max(0, h_u - 2 t) (l2: the squared distance, padding +inf).
+template <int METRIC>
+__global__ __launch_bounds__(256) void topk_merge_kernel(const u64 *part, int n_sub, int k, const int32_t *rows, const float *rowv, int32_t *out_col,
+                                                         float *out_score) {
     __shared__ u64 cur[TK_MAX_K], nb[TK_MAX_K];
     __shared__ u64 heads[256];
     const int tid = threadIdx.x, row = blockIdx.x;
@@ -262,7 +304,10 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const u64 *part, int n_
     if (tid < k) {
         const u64 key = cur[tid];
         out_col[(int64_t)row * k + tid] = key ? (int32_t)~(uint32_t)key : -1;
-        out_score[(int64_t)row * k + tid] = key ? key_score(key) : -INFINITY;
+        float x = key ? key_score(key) : -INFINITY;
+        if (METRIC == TK_COS) x = key ? x * rowv[rows[row]] : x;
+        if (METRIC == TK_L2) x = key ? fmaxf(0.f, __builtin_fmaf(-2.f, x, rowv[rows[row]])) : INFINITY;
+        out_score[(int64_t)row * k + tid] = x;
     }
 }
 
@@ -290,32 +335,73 @@ int ensure_sorted_adjacency(gg_ctx *ctx) {
     return GG_OK;
 }
 
-}  // namespace gg
+namespace {
 
-using namespace gg;
-
-// gg_topk_scores: see include/graphgan_hip.h.
-extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
-                              int32_t *out_col, float *out_score, double *kernel_ms_out) {
-    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
-    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "gg_topk_scores: which must be 0 (generator) or 1 (discriminator)");
-    GG_CHECK(ctx, k >= 1 && k <= TK_MAX_K, GG_EINVAL, "gg_topk_scores: k = %d outside [1, %d]", k, TK_MAX_K);
-    GG_CHECK(ctx, precision == 0 || precision == 1, GG_EINVAL, "gg_topk_scores: precision must be 0 (fp32) or 1 (bf16)");
-    GG_CHECK(ctx, exclude == 0 || exclude == 1, GG_EINVAL, "gg_topk_scores: exclude must be 0 or 1");
-    GG_CHECK(ctx, out_col && out_score && (rows || n_rows >= 0) && n_rows >= 0, GG_EINVAL, "gg_topk_scores: bad argument");
-    GG_CHECK(ctx, !exclude || ctx->g_rowptr, GG_EINVAL, "gg_topk_scores: exclude = 1 needs the training graph (gg_set_graph_csr)");
+// One pass: the tile stream of the precision's instance <METRIC, CAND>, then the merge.
+template <int METRIC, bool CAND>
+void launch_pass(gg_ctx *ctx, const Model &M, int precision, const Bf16Shape &bs, const uint4 *Eb, size_t dyn, int splits, int cps, const TopkOut &o,
+                 int32_t *d_col, float *d_score) {
     const int n = ctx->n_node, ld = ctx->ld;
-    GG_CHECK(ctx, precision == 0 || ctx->n_emb <= 512, GG_EINVAL, "gg_topk_scores: bf16 supports n_emb <= 512 (got %d)", ctx->n_emb);
+    const dim3 grid(splits, cdiv(o.n_rows, 32));
+    if (precision == 0 && dyn > 48 * 1024) (void)hipFuncSetAttribute((const void *)topk_f32_kernel<METRIC, CAND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (precision == 0) {
+        hipLaunchKernelGGL((topk_f32_kernel<METRIC, CAND>), grid, dim3(256), dyn, ctx->stream, M.E, n, ld, cps, o);
+    } else if (bs.KS == 4) {
+        hipLaunchKernelGGL((topk_bf16_kernel<4, METRIC, CAND>), grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+    } else if (bs.KS == 8) {
+        hipLaunchKernelGGL((topk_bf16_kernel<8, METRIC, CAND>), grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+    } else if (bs.KS == 16) {
+        hipLaunchKernelGGL((topk_bf16_kernel<16, METRIC, CAND>), grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+    } else {
+        hipLaunchKernelGGL((topk_bf16_kernel<32, METRIC, CAND>), grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+    }
+    hipLaunchKernelGGL(topk_merge_kernel<METRIC>, dim3(o.n_rows), dim3(256), 0, ctx->stream, (const u64 *)o.part, o.n_sub, o.k, o.rows, o.colv, d_col, d_score);
+}
+
+// gg_topk_scores (fn names it; metric = dot, no candidate set, exclude 0 / 1: the instance <TK_DOT, false>) and gg_topk_metric.
+int topk_run(gg_ctx *ctx, const char *fn, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t metric,
+             int32_t exclude, int32_t max_exclude, const int32_t *cand_nodes, int64_t n_cand, int32_t *out_col, float *out_score, double *kernel_ms_out) {
+    if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
+    GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "%s: which must be 0 (generator) or 1 (discriminator)", fn);
+    GG_CHECK(ctx, k >= 1 && k <= TK_MAX_K, GG_EINVAL, "%s: k = %d outside [1, %d]", fn, k, TK_MAX_K);
+    GG_CHECK(ctx, precision == 0 || precision == 1, GG_EINVAL, "%s: precision must be 0 (fp32) or 1 (bf16)", fn);
+    GG_CHECK(ctx, metric == TK_DOT || metric == TK_COS || metric == TK_L2, GG_EINVAL, "%s: metric must be 0 (dot), 1 (cosine) or 2 (l2)", fn);
+    if (max_exclude == 1) GG_CHECK(ctx, exclude == 0 || exclude == 1, GG_EINVAL, "%s: exclude must be 0 or 1", fn);
+    else GG_CHECK(ctx, exclude >= 0 && exclude <= 2, GG_EINVAL, "%s: exclude must be 0, 1 (self and training neighbours) or 2 (self)", fn);
+    GG_CHECK(ctx, out_col && out_score && (rows || n_rows >= 0) && n_rows >= 0, GG_EINVAL, "%s: bad argument", fn);
+    GG_CHECK(ctx, !cand_nodes || n_cand >= 0, GG_EINVAL, "%s: n_cand = %lld is negative", fn, (long long)n_cand);
+    GG_CHECK(ctx, exclude != 1 || ctx->g_rowptr, GG_EINVAL, "%s: exclude = 1 needs the training graph (gg_set_graph_csr)", fn);
+    const int n = ctx->n_node, ld = ctx->ld;
+    GG_CHECK(ctx, precision == 0 || ctx->n_emb <= 512, GG_EINVAL, "%s: bf16 supports n_emb <= 512 (got %d)", fn, ctx->n_emb);
     const size_t dyn = sizeof(float) * 32 * (size_t)(ld + 1);
-    GG_CHECK(ctx, precision == 1 || dyn <= 140 * 1024, GG_EINVAL, "gg_topk_scores: fp32 supports n_emb <= 1116 (got %d)", ctx->n_emb);
+    GG_CHECK(ctx, precision == 1 || dyn <= 140 * 1024, GG_EINVAL, "%s: fp32 supports n_emb <= 1116 (got %d)", fn, ctx->n_emb);
     if (!rows) n_rows = n;
     if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (max_exclude == 1) {
+        if (const int rc = check_row_ids(ctx, fn, rows, n_rows)) return rc;
+    } else {
+        if (rows)
+            for (int i = 0; i < n_rows; ++i)
+                GG_CHECK(ctx, rows[i] >= 0 && rows[i] < n, GG_EINVAL, "%s: rows[%d] = %d out of range [0, %d)", fn, i, rows[i], n);
+        if (cand_nodes)
+            for (int64_t i = 0; i < n_cand; ++i)
+                GG_CHECK(ctx, cand_nodes[i] >= 0 && cand_nodes[i] < n, GG_EINVAL, "%s: cand_nodes[%lld] = %d out of range [0, %d)", fn, (long long)i,
+                         cand_nodes[i], n);
+    }
     if (n_rows == 0) return GG_OK;
-    if (const int rc = check_row_ids(ctx, "gg_topk_scores", rows, n_rows)) return rc;
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    if (exclude) {
+    if (exclude == 1) {
         const int rc = ensure_sorted_adjacency(ctx);
         if (rc != GG_OK) return rc;
+    }
+    // the instances with a bitmap also carry exclude = 2's test; without a candidate set they get the full set
+    const bool bitmap = cand_nodes != nullptr || exclude == 2;
+    const int n_words = cdiv(n, 32);
+    std::vector<uint32_t> member;
+    if (bitmap) {
+        member.assign(n_words, cand_nodes ? 0u : 0xffffffffu);
+        if (cand_nodes)
+            for (int64_t i = 0; i < n_cand; ++i) member[cand_nodes[i] >> 5] |= 1u << (cand_nodes[i] & 31);
     }
     const Bf16Shape bs = bf16_shape(ctx->n_emb);
     const int chunk = std::min(n_rows, TK_CHUNK);
@@ -323,15 +409,17 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
     const ColumnSplit cs = column_split(n, cdiv(chunk, 32), 2048, (int)(TK_PART_CAP / ((size_t)chunk * 4 * k * sizeof(u64))));
     const int splits = cs.splits, cps = cs.cols_per_split, n_sub = 4 * splits;
     const Model &M = ctx->model[which];
-    DevBuf d_rows, d_part, d_col, d_score, d_bf;
-    auto rel = [&]() { d_rows.release(); d_part.release(); d_col.release(); d_score.release(); d_bf.release(); };
+    DevBuf d_rows, d_part, d_col, d_score, d_bf, d_colv, d_member;
+    auto rel = [&]() { d_rows.release(); d_part.release(); d_col.release(); d_score.release(); d_bf.release(); d_colv.release(); d_member.release(); };
     hipError_t e = d_rows.reserve(sizeof(int32_t) * chunk);
     if (e == hipSuccess) e = d_part.reserve(sizeof(u64) * (size_t)chunk * n_sub * k);
     if (e == hipSuccess) e = d_col.reserve(sizeof(int32_t) * (size_t)chunk * k);
     if (e == hipSuccess) e = d_score.reserve(sizeof(float) * (size_t)chunk * k);
     if (e == hipSuccess && precision == 1) e = bf16_table(ctx, which, bs.ld16, d_bf);
-    if (e != hipSuccess) { rel(); return fail(ctx, GG_ENOMEM, "gg_topk_scores: %s", hipGetErrorString(e)); }
-    if (precision == 0 && dyn > 48 * 1024) (void)hipFuncSetAttribute((const void *)topk_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (e == hipSuccess && metric != TK_DOT) e = d_colv.reserve(sizeof(float) * (size_t)n);
+    if (e == hipSuccess && bitmap) e = d_member.reserve(sizeof(uint32_t) * (size_t)n_words);
+    if (e != hipSuccess) { rel(); return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e)); }
+    if (bitmap) e = hipMemcpyAsync(d_member.p, member.data(), sizeof(uint32_t) * (size_t)n_words, hipMemcpyHostToDevice, ctx->stream);
     std::vector<int32_t> ids;
     double ms_total = 0.0;
     for (int c0 = 0; c0 < n_rows && e == hipSuccess; c0 += chunk) {
@@ -344,19 +432,23 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
         }
         e = hipMemcpyAsync(d_rows.p, src, sizeof(int32_t) * cr, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) break;
-        TopkOut o{d_rows.as<int32_t>(), cr, k, exclude ? ctx->g_rowptr : nullptr, exclude ? ctx->topk_adj.as<int32_t>() : nullptr, d_part.as<u64>(), n_sub};
-        const dim3 grid(splits, cdiv(cr, 32));
+        TopkOut o{d_rows.as<int32_t>(), cr, k, exclude == 1 ? ctx->g_rowptr : nullptr, exclude == 1 ? ctx->topk_adj.as<int32_t>() : nullptr, d_part.as<u64>(), n_sub,
+                  d_colv.as<float>(), d_member.as<uint32_t>(), exclude == 2 ? 1 : 0};
         (void)hipEventRecord(ctx->ev0, ctx->stream);
-        if (precision == 0) {
-            hipLaunchKernelGGL(topk_f32_kernel, grid, dim3(256), dyn, ctx->stream, M.E, n, ld, cps, o);
-        } else {
-            const uint4 *Eb = (const uint4 *)d_bf.p;
-            if (bs.KS == 4) hipLaunchKernelGGL(topk_bf16_kernel<4>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
-            else if (bs.KS == 8) hipLaunchKernelGGL(topk_bf16_kernel<8>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
-            else if (bs.KS == 16) hipLaunchKernelGGL(topk_bf16_kernel<16>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
-            else hipLaunchKernelGGL(topk_bf16_kernel<32>, grid, dim3(256), 0, ctx->stream, Eb, n, cps, o);
+        if (c0 == 0 && metric != TK_DOT) {  // h (and from it w) of all columns, once per call, in front of the passes
+            if (precision == 0) hipLaunchKernelGGL(sil_norm_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, M.E, ld, (const int32_t *)nullptr, n, d_colv.as<float>());
+            else hipLaunchKernelGGL(sil_norm_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, M.E, ld, (const int32_t *)nullptr, n, d_colv.as<float>());
+            if (metric == TK_COS) hipLaunchKernelGGL(topk_rsqrt_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_colv.as<float>(), n);
         }
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(cr), dim3(256), 0, ctx->stream, (const u64 *)d_part.p, n_sub, k, d_col.as<int32_t>(), d_score.as<float>());
+        const uint4 *Eb = (const uint4 *)d_bf.p;
+        int32_t *oc = d_col.as<int32_t>();
+        float *os = d_score.as<float>();
+        if (metric == TK_DOT && !bitmap) launch_pass<TK_DOT, false>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
+        else if (metric == TK_DOT) launch_pass<TK_DOT, true>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
+        else if (metric == TK_COS && !bitmap) launch_pass<TK_COS, false>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
+        else if (metric == TK_COS) launch_pass<TK_COS, true>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
+        else if (!bitmap) launch_pass<TK_L2, false>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
+        else launch_pass<TK_L2, true>(ctx, M, precision, bs, Eb, dyn, splits, cps, o, oc, os);
         (void)hipEventRecord(ctx->ev1, ctx->stream);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(out_col + (int64_t)c0 * k, d_col.p, sizeof(int32_t) * (size_t)cr * k, hipMemcpyDeviceToHost, ctx->stream);
@@ -366,8 +458,28 @@ extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, i
         if (e == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
         ms_total += ms;
     }
+    if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);  // (the bitmap's source and the buffers go away behind it)
     rel();
-    if (e != hipSuccess) return fail(ctx, GG_EHIP, "gg_topk_scores: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, GG_EHIP, "%s: %s", fn, hipGetErrorString(e));
     if (kernel_ms_out) *kernel_ms_out = ms_total;
     return GG_OK;
 }
+
+}  // namespace
+
+}  // namespace gg
+
+using namespace gg;
+
+// gg_topk_scores: see include/graphgan_hip.h.
+extern "C" int gg_topk_scores(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t exclude,
+                              int32_t *out_col, float *out_score, double *kernel_ms_out) {
+    return topk_run(ctx, "gg_topk_scores", which, rows, n_rows, k, precision, TK_DOT, exclude, 1, nullptr, 0, out_col, out_score, kernel_ms_out);
+}
+
+// gg_topk_metric: see include/graphgan_hip.h.
+extern "C" int gg_topk_metric(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t metric, int32_t exclude,
+                              const int32_t *cand_nodes, int64_t n_cand, int32_t *out_col, float *out_score, double *kernel_ms_out) {
+    return topk_run(ctx, "gg_topk_metric", which, rows, n_rows, k, precision, metric, exclude, 2, cand_nodes, n_cand, out_col, out_score, kernel_ms_out);
+}
+

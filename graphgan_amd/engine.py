@@ -528,26 +528,51 @@ class Engine:
                                          _ptr(mx), _ptr(am), _ptr(lse), ctypes.byref(ms)))
         return dict(max=mx, argmax=am, logsumexp=lse, kernel_ms=ms.value)
 
-    def topk(self, rows=None, k=10, which=0, precision="fp32", exclude=False):
-        """Streamed top-K retrieval (gg_topk_scores): for each node of ``rows`` (None: every node) the ``k`` best columns of
-        E[u] . E^T (no bias) of model ``which`` (0 = gen, 1 = dis), ordered by score descending, column ascending; with
-        ``exclude`` without u itself and u's neighbours in the resident training graph.  Rows with fewer than ``k`` eligible
-        columns are padded with -1 / -inf.  precision "fp32" (exact) or "bf16" (bf16 inputs, fp32 accumulate).  Nothing of
-        size rows x N is materialised.  Returns dict(col int32 [n_rows, k], score fp32 [n_rows, k], kernel_ms)."""
+    TOPK_METRICS = ("dot", "cosine", "l2")  # the `metric` numbers 0 .. 2 of gg_topk_metric
+
+    def topk(self, rows=None, k=10, which=0, precision="fp32", exclude=False, metric="dot", candidates=None):
+        """Streamed top-K retrieval (gg_topk_scores / gg_topk_metric): for each node of ``rows`` (None: every node) the ``k`` best
+        columns of model ``which`` (0 = gen, 1 = dis) under ``metric``:
+
+            "dot"     E[u] . E[c] (no bias), best = largest; ``score`` is the dot product
+            "cosine"  E[u] . E[c] / (|E[u]| |E[c]|), best = largest; a zero row scores 0 with everything
+            "l2"      |E[u] - E[c]|, best = SMALLEST: ``score`` is the SQUARED distance and every list is nearest first,
+                      non-decreasing
+
+        Ties go to the lower column.  ``exclude``: False every node, True without u itself and u's neighbours in the resident
+        training graph, "self" without u itself (needs no graph).  ``candidates``: node ids (free to repeat; may be empty) --
+        only they are eligible.  Rows with fewer than ``k`` eligible columns are padded with col -1 and score -inf (l2: +inf).
+        precision "fp32" (exact scores) or "bf16" (bf16 inputs, fp32 accumulate).  Nothing of size rows x N is materialised.
+        ``metric="dot"`` without candidates and with a bool ``exclude`` is gg_topk_scores, as before.
+        Returns dict(col int32 [n_rows, k], score fp32 [n_rows, k], kernel_ms)."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("topk: precision must be 'fp32' or 'bf16', got %r" % (precision,))
         if which not in (0, 1):
             raise ValueError("topk: which must be 0 (generator) or 1 (discriminator), got %r" % (which,))
         if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 256:
             raise ValueError("topk: k must be an integer in [1, 256], got %r" % (k,))
+        if metric not in self.TOPK_METRICS:
+            raise ValueError("topk: metric must be 'dot', 'cosine' or 'l2', got %r" % (metric,))
+        if isinstance(exclude, str) and exclude != "self":
+            raise ValueError("topk: exclude must be False, True or 'self', got %r" % (exclude,))
         k = int(k)
         rows_a = None if rows is None else _i32(rows).reshape(-1)
         n_rows = self.n_node if rows_a is None else len(rows_a)
         col = np.empty((n_rows, k), dtype=np.int32)
         score = np.empty((n_rows, k), dtype=np.float32)
         ms = ctypes.c_double()
-        self._ck(lib.gg_topk_scores(self._ctx, which, _ptr(rows_a), n_rows, k, {"fp32": 0, "bf16": 1}[precision], int(bool(exclude)),
-                                    _ptr(col), _ptr(score), ctypes.byref(ms)))
+        prec = {"fp32": 0, "bf16": 1}[precision]
+        if metric == "dot" and candidates is None and not isinstance(exclude, str):
+            self._ck(lib.gg_topk_scores(self._ctx, which, _ptr(rows_a), n_rows, k, prec, int(bool(exclude)), _ptr(col), _ptr(score), ctypes.byref(ms)))
+        else:
+            n_cand, cand_a = 0, None
+            if candidates is not None:
+                cand_a = _i32(candidates).reshape(-1)
+                n_cand = len(cand_a)
+                if n_cand == 0:
+                    cand_a = np.zeros(1, dtype=np.int32)  # (an empty set still needs a pointer: NULL means "no set")
+            self._ck(lib.gg_topk_metric(self._ctx, which, _ptr(rows_a), n_rows, k, prec, self.TOPK_METRICS.index(metric),
+                                        2 if exclude == "self" else int(bool(exclude)), _ptr(cand_a), n_cand, _ptr(col), _ptr(score), ctypes.byref(ms)))
         return dict(col=col, score=score, kernel_ms=ms.value)
 
     def rank(self, u, v, which=0, precision="fp32", exclude=False):

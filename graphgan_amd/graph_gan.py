@@ -22,6 +22,7 @@ Randomness: the reference draws from the unseeded global numpy RNG (Q5); here th
 uses Philox keyed by ``config.engine_seed`` and the host decisions (root selection, batch order)
 use ``numpy.random.RandomState(engine_seed)``, so runs are reproducible.
 """
+import math
 import os
 import sys
 import time
@@ -51,6 +52,7 @@ from graphgan_amd.evaluation import node_classification as nc  # noqa: E402
 from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
 from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
 from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
+from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -108,6 +110,23 @@ def _check_emb_spectrum(cfg):
         raise ValueError("engine_emb_spectrum needs at least two nodes with a training edge: %r has %d" % (path, n))
 
 
+def _check_node_knn(cfg):
+    """the k-NN lines need the labels file, under any app, and at most as many neighbours as the split has training nodes (checked
+    before anything is computed)"""
+    if not _cfg(cfg, "engine_nc_knn", False):
+        return
+    path = getattr(cfg, "labels_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_nc_knn needs labels: config.labels_filename does not exist (%r)" % (path,))
+    metric = _cfg(cfg, "engine_knn_metric", "cosine")
+    if metric not in nknn.METRICS:
+        raise ValueError("engine_knn_metric must be 'dot', 'cosine' or 'l2', got %r" % (metric,))
+    with open(path, "r") as f:
+        n_labelled = sum(1 for line in f if line.split())  # (utils.read_labels: one node per non-blank line)
+    n_train = int(math.ceil(float(_cfg(cfg, "engine_nc_train_ratio", 0.9)) * n_labelled))
+    nknn.check_k(_cfg(cfg, "engine_knn_k", 10), n_train)
+
+
 class GraphGAN(object):
     def __init__(self, cfg=None):
         self.config = cfg if cfg is not None else config
@@ -119,6 +138,7 @@ class GraphGAN(object):
         _check_link_rank(cfg)
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
+        _check_node_knn(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -498,6 +518,7 @@ class GraphGAN(object):
         _check_link_rank(cfg)
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
+        _check_node_knn(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -577,6 +598,17 @@ class GraphGAN(object):
             for i in range(2):
                 ese = espec.EmbeddingSpectrumEval(cfg.emb_filenames[i], cfg.train_filename, self.n_node, cfg.n_emb, engine=self.engine, which=i)
                 results.append(espec.format_results(cfg.modes[i], ese.eval_embedding_spectrum()))
+        if _cfg(cfg, "engine_nc_knn", False):
+            # k-NN classification of the test nodes of the classifier's split among its training nodes (one gg_topk_metric query
+            # over that candidate set, the vote on the host): one line per mode, "gen_knn:acc=<a> macro_f1=<f> k=<k> metric=<m>
+            # n_train=<n> n_test=<n>" (without an engine: the same definition in float64 on the .emb text)
+            for i in range(2):
+                emd = None if self.engine is not None else utils.read_embeddings(cfg.emb_filenames[i], n_node=self.n_node, n_embed=cfg.n_emb)
+                nke = nknn.NodeKnnEval(cfg.labels_filename, self.n_node, cfg.n_emb, engine=self.engine, emd=emd, which=i,
+                                       k=_cfg(cfg, "engine_knn_k", 10), metric=_cfg(cfg, "engine_knn_metric", "cosine"),
+                                       precision=_cfg(cfg, "engine_knn_precision", "fp32"),
+                                       train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed)
+                results.append(nknn.format_results(cfg.modes[i], nke.eval_node_knn()))
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -623,6 +623,42 @@ int gg_silhouette(gg_ctx *ctx, int which, const int32_t *nodes, const int32_t *a
 int gg_gram(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, const float *center /* [d] or NULL */,
             double *sums_out /* [d] or NULL */, double *gram_out /* [d * d] row-major or NULL */, double *ms_out);
 
+/* ---- top-K under a metric and over a candidate set (additive entry point; GG_ABI_VERSION stays 9: no existing symbol, struct or
+ * behaviour changes).  gg_topk_scores' retrieval -- the same tile stream, k-lists and merge -- ordered by cosine similarity or
+ * Euclidean distance instead of the raw dot product, optionally restricted to a set of candidate nodes: "which nodes are most
+ * similar to this one", and the neighbour query of a k-NN classifier.  For each requested node u (rows == NULL: every node,
+ * n_rows ignored; repeated rows allowed) and table E of model `which`, every operation in fp32, in this order:
+ *   s(u, c)     the bits the tile stream of `precision` gives for row u, column c, exactly as in gg_topk_scores;
+ *   h_c         |x_c|^2: the k-ordered fmaf chain from 0.0 of row c with itself (precision 1: over the bf16-ROUNDED row, as in
+ *               gg_silhouette), computed for all n_node columns once per call, in front of the passes;
+ *   metric 0    (dot)     t = s;                                     reported score t.  With cand_nodes == NULL and exclude in
+ *               {0, 1} every output bit equals gg_topk_scores';
+ *   metric 1    (cosine)  w_c = 1.0f / sqrtf(h_c) (a correctly rounded square root, one IEEE division; w_c = 0 where h_c == 0);
+ *               t = s * w_c, ONE multiply;                           reported score t * w_u, ONE multiply where the merged list is
+ *               written out.  A zero row or a zero column scores 0;
+ *   metric 2    (l2)      t = fmaf(-0.5f, h_c, s);                   reported value the SQUARED distance
+ *               fmaxf(0.f, fmaf(-2.f, t, h_u)).  The list is NEAREST FIRST;
+ *   order       t descending, column ascending, -0 counting as +0 (the key ord(t) << 32 | ~col of gg_topk_scores).  The reported
+ *               value is a monotone image of t under a single rounding (w_u >= 0; -2 < 0), so every returned list is
+ *               non-increasing (dot, cosine) or non-decreasing (l2); columns with equal t stand in ascending order, also where
+ *               their reported values are equal;
+ *   eligible    the AND of two conditions.  exclude = 0: every node; 1: not u and not u's neighbours in the resident training
+ *               graph (gg_set_graph_csr; without a graph: GG_EINVAL); 2: not u itself (needs no graph).  cand_nodes != NULL: only
+ *               the n_cand listed nodes (ids in [0, n_node), free to repeat; n_cand = 0: nothing is eligible); the library turns
+ *               the ids into an n_node-bit bitmap on the device.  Like the adjacency, the bit is read only where a column is about
+ *               to enter a list: an ineligible column never enters one and never raises a list's threshold;
+ *   result      out_col[n_rows][k] (int32) and out_score[n_rows][k] (fp32), row-major; a row with fewer than k eligible columns
+ *               is padded with col -1 and score -inf (metric 2: +inf).
+ * limits       1 <= k <= 256, metric in {0, 1, 2}, exclude in {0, 1, 2}, precision 0 or 1, n_cand >= 0, the widths of the tile
+ *              stream (fp32 n_emb <= 1116, bf16 n_emb <= 512), ids in [0, n_node).  Anything else: GG_EINVAL, the gg_last_error
+ *              text names gg_topk_metric and the limit (for an id: the array and the FIRST bad index), nothing is launched.
+ *              Non-finite values: unspecified.
+ * determinism  no atomics: the same inputs and table give the same bits.  A row's outputs depend on the row, the set and k alone.
+ * kernel_ms_out (may be NULL): HIP-event time of the norm pass, the tile streams and the merges (the bf16 copy excluded, as in
+ * gg_topk_scores).  Temporary device buffers are freed on every exit path. */
+int gg_topk_metric(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t metric,
+                   int32_t exclude, const int32_t *cand_nodes, int64_t n_cand, int32_t *out_col, float *out_score, double *kernel_ms_out);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);

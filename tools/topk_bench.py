@@ -4,7 +4,10 @@ process (gg_all_score_reduce, logsumexp off: the same tile stream with the cheap
     python tools/topk_bench.py [n_node] [n_emb] [n_rows] [k]        (default 10^7 256 4096 100)
 One JSON line: per precision kernel_ms (best of 3), call_s, TFLOP/s (2 rows N d, K7's flop count) and its fraction of the
 dense MFMA peak; the max-only kernel_ms and the ratio to it; exclude = 1 on the synthetic power-law graph (no target); and a
-parity leg on 32 rows (fp32: equal to the oracle's fp32 rows, stably sorted; bf16: fp64 numpy on the bf16-rounded table)."""
+parity leg on 32 rows (fp32: equal to the oracle's fp32 rows, stably sorted; bf16: fp64 numpy on the bf16-rounded table).
+    python tools/topk_bench.py --metric cosine [--metric l2] [n_node] [n_emb] [n_rows] [k]
+measures the metric consumer (gg_topk_metric) instead: per precision the dot leg (gg_topk_scores) and every named metric,
+ALTERNATING in the same process, best of 3 by HIP events, and each metric's ratio to the dot leg (expected: at most about 1.1)."""
 import json
 import os
 import sys
@@ -17,10 +20,18 @@ sys.path.insert(0, ROOT)
 import graphgan_amd as ga  # noqa: E402
 from graphgan_amd import workloads  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-d = int(sys.argv[2]) if len(sys.argv) > 2 else 256
-r = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
-k = int(sys.argv[4]) if len(sys.argv) > 4 else 100
+argv, metrics = [], []
+for i, a in enumerate(sys.argv[1:], 1):
+    if a == "--metric":
+        metrics.append(sys.argv[i + 1])
+    elif sys.argv[i - 1] != "--metric":
+        argv.append(a)
+if any(m not in ("cosine", "l2", "dot") for m in metrics):
+    sys.exit("--metric must be cosine, l2 or dot")
+n = int(argv[0]) if len(argv) > 0 else 10_000_000
+d = int(argv[1]) if len(argv) > 1 else 256
+r = int(argv[2]) if len(argv) > 2 else 4096
+k = int(argv[3]) if len(argv) > 3 else 100
 t0 = time.time()
 rowptr, col, emb, n_edges = workloads.powerlaw_workload(n, n_emb=d)
 t_gen = time.time() - t0
@@ -42,6 +53,21 @@ def best_of(fn, reps=3):
         best = res["kernel_ms"] if best is None else min(best, res["kernel_ms"])
     return best, wall, res
 
+
+if metrics:
+    # the metric legs beside the dot leg: one round = every leg once, three rounds, the best kernel_ms of each leg
+    legs = ["dot"] + [m for m in metrics if m != "dot"]
+    for prec in ("fp32", "bf16"):
+        eng.topk(rows[:64], k=k, precision=prec)  # (the bf16 copy's first build, the kernels' first load)
+        runs = {m: [] for m in legs}
+        for _ in range(3):
+            for m in legs:
+                runs[m].append(eng.topk(rows, k=k, precision=prec, metric=m)["kernel_ms"])
+        out[prec] = {m: {"kernel_ms": min(v), "runs_ms": v, "ratio_to_dot": min(v) / min(runs["dot"])} for m, v in runs.items()}
+        out[prec]["expected_ratio_at_most"] = 1.1
+    eng.close()
+    print(json.dumps(out))
+    sys.exit(0)
 
 for prec, peak in (("fp32", 157.3), ("bf16", 2500.0)):
     ref_ms, _, _ = best_of(lambda: eng.all_score_reduce(rows, precision=prec, logsumexp=False))
