@@ -123,6 +123,12 @@ engine_nc_knn = False
 engine_knn_k = 10               # neighbours that vote, 1 .. 256
 engine_knn_metric = "cosine"    # "cosine" | "l2" | "dot"
 engine_knn_precision = "fp32"   # neighbour scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
+# neighbourhood link-prediction baselines (evaluation/link_heuristics.py): with engine_lp_heuristics = True evaluation() appends, under
+# any app, after the *_knn lines and before gen_nll, ONE line "graph_lp:cn= jaccard= aa= ra= pa= n_test=" -- the AUC of common
+# neighbours, Jaccard, Adamic-Adar, resource allocation and preferential attachment on the TRAINING graph over the test edges and
+# test negatives (one pair-neighbour sweep on the device, gg_pair_neighbors).  No embedding takes part, so the line is computed at
+# the first evaluation and repeated at every later one: the floor the *_lp lines stand on.  Needs test_filename and test_neg_filename.
+engine_lp_heuristics = False
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

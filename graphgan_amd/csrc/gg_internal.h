@@ -309,6 +309,14 @@ struct gg_ctx {
     gg::DevBuf topk_adj;
     bool topk_adj_valid = false;
 
+    // gg_pair_neighbors / gg_distinct_degrees (pair_neighbors.hip): the SET adjacency of the resident graph -- every list sorted,
+    // distinct and without the node itself, under row offsets of its own (host copy: h_pn_ptr) -- built by ensure_set_adjacency on
+    // first use; dropped by gg_set_graph_csr
+    gg::DevBuf pn_ptr, pn_adj;
+    std::vector<int64_t> h_pn_ptr;
+    int32_t pn_max_deg = 0;
+    bool pn_valid = false;
+
     // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
     // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr
     gg::DevBuf gs_es, gs_cpre;
@@ -359,6 +367,7 @@ int fail(gg_ctx *ctx, int code, const char *fmt, ...);
 // exclusive scan of n int32 counts into n+1 int64 offsets (prepare.hip)
 int device_exclusive_scan(gg_ctx *ctx, const int32_t *cnt, int64_t *ptr, int64_t n);
 int ensure_sorted_adjacency(gg_ctx *ctx);  // topk_score.hip: ctx->topk_adj (every node's list sorted), built on first use
+int ensure_set_adjacency(gg_ctx *ctx);  // pair_neighbors.hip: ctx->pn_ptr / pn_adj (sorted distinct lists without the node itself), built on first use
 int ensure_g_pairs(gg_ctx *ctx);  // prepare.hip: (node_1, node_2) of the resident G walks, written on first use
 int device_compact_flags(gg_ctx *ctx, const int32_t *flag, int64_t n, int32_t *list, int64_t *total_out);  // prepare.hip
 int device_segment_rows(gg_ctx *ctx, const int32_t *cnt, int64_t n, int T, int32_t *off, int4 *list, int64_t *totals, hipStream_t stream = nullptr,

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import GGConfig, GGCounters, check, lib
 from .evaluation.embedding_spectrum import pca_cov, pca_eig
+from .evaluation import link_heuristics as _lheur
 
 
 def _ptr(a):
@@ -598,6 +599,47 @@ class Engine:
             self._ck(lib.gg_rank_scores(self._ctx, which, _ptr(u_a), _ptr(v_a), m, {"fp32": 0, "bf16": 1}[precision], int(bool(exclude)),
                                         _ptr(rank), _ptr(n_cand), _ptr(score), ctypes.byref(ms)))
         return dict(rank=rank, n_cand=n_cand, score=score, kernel_ms=ms.value)
+
+    PAIR_NEIGHBORS_CHUNK = _lib.PAIR_NEIGHBORS_CHUNK  # entries of a pair's shorter neighbour list per task of the sweep (longer lists are split)
+
+    def distinct_degrees(self):
+        """deg(x) = |N(x)| of every node of the resident training graph (gg_distinct_degrees), N(x) the distinct entries of x's
+        list other than x itself: int32 [n_node]."""
+        deg = np.empty(self.n_node, dtype=np.int32)
+        self._ck(lib.gg_distinct_degrees(self._ctx, _ptr(deg)))
+        return deg
+
+    def pair_neighbors(self, u, v, weights=None):
+        """The pair-neighbour sweep (gg_pair_neighbors): for each pair (u[i], v[i]) the common neighbours C = (N(u) & N(v)) \\ {u, v}
+        in the resident training graph -- neighbour SETS: duplicates and self-loops of the lists do not count; u == v gives
+        C = N(u).  ``weights``: None or a uint64 array [n_w, n_node], n_w <= 4, of fixed-point node weights; they are summed over
+        C as unsigned 64-bit integers, so exchanging the ends, permuting the pairs or running again changes no bit
+        (max(weights) * max(deg) must fit in 63 bits).  No embedding table is read.  Returns dict(cn int32 [m] = |C|, deg_u int32
+        [m], deg_v int32 [m], wsum uint64 [n_w, m], kernel_ms)."""
+        u_a, v_a = _i32(u).reshape(-1), _i32(v).reshape(-1)
+        if len(u_a) != len(v_a):
+            raise ValueError("pair_neighbors: u and v must have the same length, got %d and %d" % (len(u_a), len(v_a)))
+        w_a, n_w = None, 0
+        if weights is not None:
+            w_a = np.ascontiguousarray(weights, dtype=np.uint64)
+            if w_a.ndim != 2 or w_a.shape[1] != self.n_node:
+                raise ValueError("pair_neighbors: weights must be a uint64 array [n_w, %d], got shape %r" % (self.n_node, w_a.shape))
+            n_w = int(w_a.shape[0])
+        m = len(u_a)
+        cn, deg_u, deg_v = (np.empty(m, dtype=np.int32) for _ in range(3))
+        wsum = np.empty((n_w, m), dtype=np.uint64)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_pair_neighbors(self._ctx, _ptr(u_a), _ptr(v_a), m, _ptr(w_a) if n_w else None, n_w, _ptr(cn), _ptr(deg_u), _ptr(deg_v),
+                                       _ptr(wsum) if n_w else None, ctypes.byref(ms)))
+        return dict(cn=cn, deg_u=deg_u, deg_v=deg_v, wsum=wsum, kernel_ms=ms.value)
+
+    def link_heuristics(self, u, v):
+        """The neighbourhood link-prediction indices of the pairs (u[i], v[i]) on the resident training graph
+        (evaluation/link_heuristics.py): one ``pair_neighbors`` sweep with the fixed-point Adamic-Adar and resource-allocation
+        weights of ``link_heuristics.node_weights(distinct_degrees())``.  Returns dict(cn int64 [m], jaccard float64 [m], aa
+        float64 [m], ra float64 [m], pa int64 [m]); aa and ra are within cn * 2^-41 of the un-quantised sums."""
+        res = self.pair_neighbors(u, v, _lheur.node_weights(self.distinct_degrees()))
+        return _lheur.indices(res["cn"], res["deg_u"], res["deg_v"], res["wsum"])
 
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node

@@ -53,6 +53,7 @@ from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
 from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
 from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
 from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
+from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -75,6 +76,16 @@ def _check_lp_classifier(cfg):
         path = getattr(cfg, name, None)
         if not path or not os.path.isfile(path):
             raise ValueError("engine_lp_classifier needs test edges and test negatives: config.%s does not exist (%r)" % (name, path))
+
+
+def _check_lp_heuristics(cfg):
+    """the neighbourhood baseline line needs both test files, under any app (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_lp_heuristics", False):
+        return
+    for name in ("test_filename", "test_neg_filename"):
+        path = getattr(cfg, name, None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("engine_lp_heuristics needs test edges and test negatives: config.%s does not exist (%r)" % (name, path))
 
 
 def _check_link_rank(cfg):
@@ -139,6 +150,7 @@ class GraphGAN(object):
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
+        _check_lp_heuristics(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -156,6 +168,7 @@ class GraphGAN(object):
         self.root_nodes = [int(r) for r in parallel.shard_roots(np.arange(self.n_node), self.rank, self.world,
                                                                 weights=deg if self.world > 1 else None)]
         self._prepare_no = 0
+        self._graph_lp_line = None  # the graph_lp results line (engine_lp_heuristics): a function of the files alone, computed once
 
         self.seed = int(_cfg(cfg, "engine_seed", 0))
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
@@ -519,6 +532,7 @@ class GraphGAN(object):
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
+        _check_lp_heuristics(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -609,6 +623,14 @@ class GraphGAN(object):
                                        precision=_cfg(cfg, "engine_knn_precision", "fp32"),
                                        train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed)
                 results.append(nknn.format_results(cfg.modes[i], nke.eval_node_knn()))
+        if _cfg(cfg, "engine_lp_heuristics", False):
+            # neighbourhood baselines on the training graph (gg_pair_neighbors): ONE line, "graph_lp:cn=<auc> jaccard=<auc> aa=<auc>
+            # ra=<auc> pa=<auc> n_test=<n>" -- the graph is the same for both tables and every evaluation, so the line is computed
+            # once and repeated (without an engine: the same integers from numpy on the training file, the same string)
+            if getattr(self, "_graph_lp_line", None) is None:
+                lhe = lheur.LinkHeuristicsEval(cfg.train_filename, cfg.test_filename, cfg.test_neg_filename, self.n_node, engine=self.engine)
+                self._graph_lp_line = lheur.format_results(lhe.eval_link_heuristics())
+            results.append(self._graph_lp_line)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -659,6 +659,37 @@ int gg_gram(gg_ctx *ctx, int which, const int32_t *nodes, int64_t m, const float
 int gg_topk_metric(gg_ctx *ctx, int32_t which, const int32_t *rows, int32_t n_rows, int32_t k, int32_t precision, int32_t metric,
                    int32_t exclude, const int32_t *cand_nodes, int64_t n_cand, int32_t *out_col, float *out_score, double *kernel_ms_out);
 
+/* ---- pair-neighbour sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * The device part of the neighbourhood link-prediction indices -- common neighbours, Jaccard, Adamic-Adar, resource allocation,
+ * preferential attachment -- on the resident training graph (gg_set_graph_csr).  No embedding table is read.
+ *   N(x)        the neighbour SET of node x: the distinct entries of x's resident list other than x itself (the resident lists
+ *               keep duplicates and list a self-loop twice; the sets do not);
+ *   deg(x)      |N(x)|;
+ *   C(u, v)     (N(u) & N(v)) \ {u, v}; u == v is allowed and follows the formulas: C(u, u) = N(u).
+ * gg_distinct_degrees: deg[x] = deg(x) for every node.
+ * gg_pair_neighbors, for the pairs i = 0 .. m - 1:
+ *   cn[i]       = |C(u_i, v_i)|,   deg_u[i] = deg(u_i),   deg_v[i] = deg(v_i);
+ *   wsum[j * m + i] = sum over w in C(u_i, v_i) of weights[j * n_node + w],  j = 0 .. n_w - 1: a sum of UNSIGNED 64-BIT INTEGERS --
+ *               exact, independent of the order of the terms and of how the work was split.  Fixed-point node weights make the
+ *               result a bit contract without prescribing a reduction shape: exchanging u and v, permuting the pairs, running
+ *               again or splitting one pair over several wavefronts changes no bit.
+ * The sets are kept as an adjacency of their own (sorted lists under int64 row offsets), built on the host on first use after
+ * gg_set_graph_csr, which drops it.  A group of 4, 16 or 64 lanes per pair -- chosen from the pair's shorter list -- walks that
+ * list and looks each entry up in the longer one by binary search; a pair whose shorter list is longer than 512 entries is
+ * split into tasks of 512 entries that add into the zeroed outputs with integer atomics.
+ * limits       0 <= n_w <= 4; m >= 0 (m == 0 succeeds and writes nothing); ids in [0, n_node); cn, deg_u and deg_v not NULL;
+ *              weights and wsum not NULL when n_w > 0 (ignored when n_w == 0); max(weights) * max(deg) must fit in 63 bits
+ *              (checked on the host, so no sum can wrap); a resident graph.  Anything else: GG_EINVAL, the gg_last_error text
+ *              names the entry point (for an id: the array and the FIRST bad index), nothing is launched.
+ * determinism  integer arithmetic only: the same inputs give the same bits.
+ * weights are uploaded by every call.  kernel_ms (may be NULL): HIP-event time of the sweep kernels on the context's stream.
+ * Temporary device buffers are freed on every exit path. */
+int gg_distinct_degrees(gg_ctx *ctx, int32_t *deg /* [n_node] */);
+int gg_pair_neighbors(gg_ctx *ctx, const int32_t *u, const int32_t *v, int64_t m,
+                      const uint64_t *weights /* [n_w * n_node] or NULL */, int32_t n_w /* 0 .. 4 */,
+                      int32_t *cn /* [m] */, int32_t *deg_u /* [m] */, int32_t *deg_v /* [m] */,
+                      uint64_t *wsum /* [n_w * m] or NULL when n_w == 0 */, double *kernel_ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
