@@ -31,6 +31,8 @@ GG_ROOT_OK, GG_ROOT_ABORTED, GG_ROOT_EMPTY = 0, 1, 2
 GG_GS_FOR_D, GG_GS_Q3_STORE = 1, 2
 GRAM_MAX_GRID = 512  # == GRAM_MAX_GRID of csrc/gram.hip: workgroups of a gg_gram sweep at most (its grid is min(this, ceil(m / 64)))
 PAIR_NEIGHBORS_CHUNK = 512  # == PN_CHUNK of csrc/pair_neighbors.hip: a pair whose shorter neighbour list is longer is split into tasks of this many entries
+NEIGHBOR_SUM_CHUNK = 512  # == GP_CHUNK of csrc/graph_prop.hip: a node with more neighbours is split into tasks of this many entries
+NEIGHBOR_SUM_MAX_COL = 128  # == GP_MAX_COL: columns of a neighbour sum / classes of a label spreading at most
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
                GG_ENOMEM: "GG_ENOMEM", GG_EIO: "GG_EIO"}
 
@@ -120,6 +122,8 @@ SIGNATURES = {
     "gg_rank_scores": (ctypes.c_int, [_P, _i32, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P]),
     "gg_distinct_degrees": (ctypes.c_int, [_P, _P]),
     "gg_pair_neighbors": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P, _P]),
+    "gg_neighbor_sum": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _i64, _P, _P]),
+    "gg_label_spread": (ctypes.c_int, [_P, _P, _P, _i64, _i32, ctypes.c_double, _i32, _P, _P, _P, _i64, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
     "gg_pretrain_set_walk_bias": (ctypes.c_int, [_P, _u32, _u32, _u32]),

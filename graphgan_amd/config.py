@@ -129,6 +129,15 @@ engine_knn_precision = "fp32"   # neighbour scores in exact "fp32" or "bf16" (ma
 # test negatives (one pair-neighbour sweep on the device, gg_pair_neighbors).  No embedding takes part, so the line is computed at
 # the first evaluation and repeated at every later one: the floor the *_lp lines stand on.  Needs test_filename and test_neg_filename.
 engine_lp_heuristics = False
+# label-spreading baseline of node classification (evaluation/label_propagation.py): with engine_nc_graph_baseline = True evaluation()
+# appends, under any app, after the graph_lp line and before gen_nll, ONE line "graph_nc:acc= macro_f1= alpha= iters= delta= unreached=
+# n_train= n_test=" (with engine_nc_multilabel: "acc= micro_f1= macro_f1= ...", protocol "topk" only) -- F <- alpha S F + (1 - alpha) Y on the
+# TRAINING graph from the training labels of the classifier's split (engine_nc_train_ratio, engine_seed), iterated on the device
+# (gg_label_spread).  No embedding takes part, so the line is computed at the first evaluation and repeated at every later one: what
+# the graph and the labels alone predict.  Needs labels_filename.  Both defaults are provisional: they have not been tuned on any dataset.
+engine_nc_graph_baseline = False
+engine_lsp_alpha = 0.9          # in (0, 1): the share a node takes from its neighbours
+engine_lsp_iters = 30           # iterations (a label travels one hop per iteration)
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

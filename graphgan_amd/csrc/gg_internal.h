@@ -317,6 +317,14 @@ struct gg_ctx {
     int32_t pn_max_deg = 0;
     bool pn_valid = false;
 
+    // gg_neighbor_sum / gg_label_spread (graph_prop.hip): the task plan of the all-nodes neighbour-sum sweep over that set adjacency --
+    // tasks (row, first entry, stage row or -1) and hubs (row, first stage row, chunks) -- a function of the graph alone: built on
+    // first use, dropped by gg_set_graph_csr beside pn_valid; gp_stage holds the hubs' partial rows of the call in flight
+    gg::DevBuf gp_task, gp_hub, gp_stage;
+    int32_t gp_n_task = 0, gp_n_hub = 0;
+    int64_t gp_n_stage = 0;
+    bool gp_valid = false;
+
     // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
     // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr
     gg::DevBuf gs_es, gs_cpre;

@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import GGConfig, GGCounters, check, lib
 from .evaluation.embedding_spectrum import pca_cov, pca_eig
 from .evaluation import link_heuristics as _lheur
+from .evaluation import label_propagation as _lprop
 
 
 def _ptr(a):
@@ -640,6 +641,64 @@ class Engine:
         float64 [m], ra float64 [m], pa int64 [m]); aa and ra are within cn * 2^-41 of the un-quantised sums."""
         res = self.pair_neighbors(u, v, _lheur.node_weights(self.distinct_degrees()))
         return _lheur.indices(res["cn"], res["deg_u"], res["deg_v"], res["wsum"])
+
+    NEIGHBOR_SUM_CHUNK = _lib.NEIGHBOR_SUM_CHUNK  # neighbours of a node per task of the neighbour-sum sweep (a node with more is split)
+
+    def _gp_scale(self, fn, name, scale):
+        if scale is None:
+            return None
+        a = np.ascontiguousarray(scale, dtype=np.float32)
+        if a.shape != (self.n_node,):
+            raise ValueError("%s: %s must be a float array [%d] or None, got shape %r" % (fn, name, self.n_node, a.shape))
+        return a
+
+    def neighbor_sum(self, X, in_scale=None, out_scale=None, nodes=None):
+        """The neighbour-sum sweep (gg_neighbor_sum) on the neighbour SETS N(v) of the resident training graph (those of
+        ``pair_neighbors``): out[i, c] = out_scale[v] * sum over w in N(v) of (in_scale[w] * X[w, c]), v = nodes[i] (``nodes`` None: every
+        node).  X is a float array [n_node, n_col], n_col <= 128; a scale of None means no multiply.  fp32: one rounded multiply per
+        gathered element, adds, one rounded multiply at the end, no fused multiply-add.  The order of a node's adds is not
+        specified, but the bits of its row depend on its neighbours, the gathered values and n_col alone: a rerun, a permuted or
+        repeated ``nodes`` and a subset return the same bits per node.  No embedding table is read.
+        Returns dict(out fp32 [m, n_col], ms)."""
+        fn = "neighbor_sum"
+        X_a = np.ascontiguousarray(X, dtype=np.float32)
+        if X_a.ndim != 2 or X_a.shape[0] != self.n_node:
+            raise ValueError("%s: X must be a float matrix [%d, n_col], got shape %r" % (fn, self.n_node, X_a.shape))
+        n_col = int(X_a.shape[1])
+        if not 1 <= n_col <= _lib.NEIGHBOR_SUM_MAX_COL:
+            raise ValueError("%s: n_col = %d outside [1, %d]" % (fn, n_col, _lib.NEIGHBOR_SUM_MAX_COL))
+        in_a, os_a = self._gp_scale(fn, "in_scale", in_scale), self._gp_scale(fn, "out_scale", out_scale)
+        nodes_a = None if nodes is None else _i32(_lprop.check_nodes(fn, "nodes", nodes, self.n_node))
+        m = self.n_node if nodes_a is None else len(nodes_a)
+        out = np.empty((m, n_col), dtype=np.float32)
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_neighbor_sum(self._ctx, _ptr(X_a), n_col, _ptr(in_a), _ptr(os_a), _ptr(nodes_a), m, _ptr(out), ctypes.byref(ms)))
+        return dict(out=out, ms=ms.value)
+
+    def label_spread(self, train_nodes, labels, n_class, alpha=0.9, iters=30, out_nodes=None):
+        """Label spreading on the resident training graph (gg_label_spread; evaluation/label_propagation.py): F_0 = Y0,
+        F_{t+1} = alpha S F_t + (1 - alpha) Y0 with S = D^-1/2 A D^-1/2 on the neighbour sets, ``iters`` iterations on the device.
+        ``labels``: an int array [m_train] (single label), a bool / 0-1 matrix [m_train, n_class] or a list of label lists
+        (multi-label); ``train_nodes`` distinct.  The coefficients are ``label_propagation.spread_coefficients`` of
+        ``distinct_degrees()``.  ``iters = T`` equals T ``neighbor_sum(F, in_scale=s)`` calls composed with float32 a * H + base, bit
+        for bit.  Returns dict(F fp32 [m_out, n_class] -- the rows of ``out_nodes``, None: every node --, delta = max |F_T - F_{T-1}|
+        over all nodes, ms)."""
+        fn = "label_spread"
+        if isinstance(n_class, bool) or int(n_class) != n_class or not 1 <= int(n_class) <= _lib.NEIGHBOR_SUM_MAX_COL:
+            raise ValueError("%s: n_class = %r outside [1, %d]" % (fn, n_class, _lib.NEIGHBOR_SUM_MAX_COL))
+        C = int(n_class)
+        _lprop.check_alpha_iters(fn, alpha, iters)
+        tr = _i32(_lprop.check_nodes(fn, "train_nodes", train_nodes, self.n_node, distinct=True))
+        bits = pack_label_bits(_lprop.label_matrix(fn, labels, len(tr), C), C)
+        out_a = None if out_nodes is None else _i32(_lprop.check_nodes(fn, "out_nodes", out_nodes, self.n_node))
+        s, a, _ = _lprop.spread_coefficients(self.distinct_degrees(), alpha)
+        m_out = self.n_node if out_a is None else len(out_a)
+        F = np.empty((m_out, C), dtype=np.float32)
+        delta, ms = ctypes.c_float(), ctypes.c_double()
+        self._ck(lib.gg_label_spread(self._ctx, _ptr(tr), _ptr(bits), len(tr), C, float(alpha), int(iters), _ptr(s), _ptr(a), _ptr(out_a), m_out,
+                                     _ptr(F), ctypes.byref(delta), ctypes.byref(ms)))
+        return dict(F=F, delta=float(delta.value), ms=ms.value)
 
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node

@@ -54,6 +54,7 @@ from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
 from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
 from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
 from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
+from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -86,6 +87,24 @@ def _check_lp_heuristics(cfg):
         path = getattr(cfg, name, None)
         if not path or not os.path.isfile(path):
             raise ValueError("engine_lp_heuristics needs test edges and test negatives: config.%s does not exist (%r)" % (name, path))
+
+
+def _check_nc_graph_baseline(cfg):
+    """the label-spreading line needs the labels file, under any app, a share in (0, 1) and at least one iteration; multi-label
+    files are scored by the "topk" protocol only (checked before anything is computed)"""
+    if not _cfg(cfg, "engine_nc_graph_baseline", False):
+        return
+    path = getattr(cfg, "labels_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_nc_graph_baseline needs labels: config.labels_filename does not exist (%r)" % (path,))
+    alpha, iters = _cfg(cfg, "engine_lsp_alpha", 0.9), _cfg(cfg, "engine_lsp_iters", 30)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) < 1.0:
+        raise ValueError("engine_lsp_alpha must lie in (0, 1), got %r" % (alpha,))
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError("engine_lsp_iters must be an integer >= 1, got %r" % (iters,))
+    if _cfg(cfg, "engine_nc_multilabel", False) and _cfg(cfg, "engine_nc_ml_protocol", "topk") != "topk":
+        raise ValueError("engine_nc_graph_baseline scores multi-label files by the 'topk' protocol only, got engine_nc_ml_protocol = %r"
+                         % (_cfg(cfg, "engine_nc_ml_protocol", "topk"),))
 
 
 def _check_link_rank(cfg):
@@ -151,6 +170,7 @@ class GraphGAN(object):
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
         _check_lp_heuristics(cfg)
+        _check_nc_graph_baseline(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -169,6 +189,7 @@ class GraphGAN(object):
                                                                 weights=deg if self.world > 1 else None)]
         self._prepare_no = 0
         self._graph_lp_line = None  # the graph_lp results line (engine_lp_heuristics): a function of the files alone, computed once
+        self._graph_nc_line = None  # the graph_nc results line (engine_nc_graph_baseline) likewise
 
         self.seed = int(_cfg(cfg, "engine_seed", 0))
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
@@ -533,6 +554,7 @@ class GraphGAN(object):
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
         _check_lp_heuristics(cfg)
+        _check_nc_graph_baseline(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -631,6 +653,18 @@ class GraphGAN(object):
                 lhe = lheur.LinkHeuristicsEval(cfg.train_filename, cfg.test_filename, cfg.test_neg_filename, self.n_node, engine=self.engine)
                 self._graph_lp_line = lheur.format_results(lhe.eval_link_heuristics())
             results.append(self._graph_lp_line)
+        if _cfg(cfg, "engine_nc_graph_baseline", False):
+            # label spreading on the training graph from the training labels of the classifier's split (gg_label_spread): ONE line,
+            # "graph_nc:acc=<a> macro_f1=<f> alpha=<a> iters=<t> delta=<d> unreached=<u> n_train=<n> n_test=<n>" (multi-label: micro_f1
+            # behind acc) -- computed once and repeated, like graph_lp (without an engine: float64 numpy on the training file)
+            if getattr(self, "_graph_nc_line", None) is None:
+                multilabel = bool(_cfg(cfg, "engine_nc_multilabel", False))
+                lse = lprop.LabelSpreadEval(cfg.train_filename, cfg.labels_filename, self.n_node, engine=self.engine,
+                                            train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed,
+                                            alpha=float(_cfg(cfg, "engine_lsp_alpha", 0.9)), iters=int(_cfg(cfg, "engine_lsp_iters", 30)),
+                                            multilabel=multilabel)
+                self._graph_nc_line = lprop.format_results(lse.eval_label_spread(), multilabel)
+            results.append(self._graph_nc_line)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

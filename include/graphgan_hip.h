@@ -690,6 +690,61 @@ int gg_pair_neighbors(gg_ctx *ctx, const int32_t *u, const int32_t *v, int64_t m
                       int32_t *cn /* [m] */, int32_t *deg_u /* [m] */, int32_t *deg_v /* [m] */,
                       uint64_t *wsum /* [n_w * m] or NULL when n_w == 0 */, double *kernel_ms /* or NULL */);
 
+/* ---- neighbour-sum sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * A CSR times dense-matrix product on the set adjacency N(v) of the resident training graph -- the one gg_pair_neighbors uses
+ * (sorted, distinct, without the node itself) -- and label spreading (Zhou et al. 2004) iterated on it.  Needs gg_set_graph_csr;
+ * no embedding table is read.
+ *
+ * gg_neighbor_sum: X fp32 [n_node, n_col], in_scale / out_scale fp32 [n_node] or NULL, nodes int32 [m] or NULL for all nodes
+ * (m is then not read and out is [n_node, n_col]); with v = nodes[i]
+ *   out[i, c] = out_scale[v] * sum over w in N(v) of (in_scale[w] * X[w, c]).
+ * NULL means "no multiply" (the bits equal those of a scale of 1.0f).
+ *   arithmetic  one separately rounded fp32 multiply per gathered element where in_scale is given, fp32 adds, one separately
+ *               rounded fp32 multiply at the end where out_scale is given; no fused multiply-add.  A node without neighbours
+ *               gives +0.
+ *   bit contract  the ORDER of a node's adds is not specified.  The bits of out for node v are a function of N(v), the gathered
+ *               rows, the scales and n_col alone: they do not depend on which other nodes were requested, on their order, on the
+ *               grid or on the run.  A rerun, a permuted `nodes`, a subset and a repeated id return the same bits per node; there
+ *               are no floating-point atomics.  Where every partial sum is exactly representable (integer inputs with sums below
+ *               2^24) the result is exact.
+ *   shape       rows are padded on the device to CP = 4 ceil(n_col / 4) floats; a row takes LPR lanes, the smallest power of two
+ *               >= CP / 4; a wavefront works on one node, its 64 / LPR lane groups each on a different neighbour, four rows in
+ *               flight per group, folded by a fixed shuffle tree.  A node with more than 512 neighbours is split into tasks of
+ *               512 entries that write partial rows into a stage; a finishing kernel adds a node's partial rows in ascending
+ *               chunk order.  The split depends on the node's degree alone.  The task plan of the all-nodes sweep is built once
+ *               per graph and dropped by gg_set_graph_csr.
+ *   limits      1 <= n_col <= 128; m >= 0 (m == 0 succeeds and writes nothing); X and out not NULL; ids in [0, n_node); a
+ *               resident graph.  Anything else: GG_EINVAL, the gg_last_error text names the entry point and the value (for an
+ *               id: the FIRST bad index), nothing is launched.
+ *
+ * gg_label_spread: F <- alpha S F + (1 - alpha) Y, S = D^-1/2 A D^-1/2 on N, from F_0 = Y0 for `iters` iterations.
+ *   train_nodes int32 [m_train] distinct; label_bits uint32 [m_train, ceil(n_class / 32)]: bit c & 31 of word c >> 5 says that
+ *   the node has label c (one bit: single label; several: multi-label); Y0[v, c] = 1 for those, else 0.
+ *   s, a        fp32 [n_node]: s[v] = fp32(1 / sqrt(deg(v))), a[v] = fp32(alpha / sqrt(deg(v))), 0 where deg(v) = 0, as the caller
+ *               rounded them (one host function serves the device and the host path); b = fp32(1 - alpha), float64 subtraction.
+ *   iteration   H = neighbor_sum(F_t, in_scale = s);  F_{t+1}[v, c] = (a[v] * H[v, c]) + (Y0[v, c] ? b : 0): two separately rounded
+ *               fp32 operations, no fused multiply-add.  The fit and gg_neighbor_sum run ONE sweep kernel (the epilogue is a
+ *               compile-time variant), so gg_label_spread(iters = T) equals T calls of gg_neighbor_sum composed on the host with
+ *               float32 a * H + base, bit for bit.
+ *   outputs     F_out[i, :] = F_T[out_nodes[i], :] (out_nodes NULL: every node, m_out is then not read); *delta =
+ *               max |F_T - F_{T-1}| over all n_node x n_class entries (fp32 subtraction; an integer maximum of non-negative float
+ *               bits on the device, so order-independent).  m_out == 0 runs the fit, writes no row and returns delta.
+ *   residency   F_t, F_{t+1} and the label masks of all nodes live on the device for the whole call; Y0 is built there from the
+ *               masks; the plan is not rebuilt or uploaded per iteration.  Nothing of size n_node x n_class crosses to the host
+ *               except F_out when out_nodes is NULL.
+ *   limits      1 <= n_class <= 128; m_train >= 0; m_out >= 0; train_nodes, label_bits, s, a not NULL; F_out not NULL when rows
+ *               are asked for; 0 < alpha < 1; iters >= 1; ids in [0, n_node); no repeated training node; no label bit at or above
+ *               n_class.  Anything else: GG_EINVAL as above.
+ * kernel_ms (may be NULL): HIP-event time of the sweep kernels (of all iterations) on the context's stream; uploads, the Y0
+ * kernel and the read-back are outside.  Temporary device buffers are freed on every exit path. */
+int gg_neighbor_sum(gg_ctx *ctx, const float *X /* [n_node, n_col] */, int32_t n_col, const float *in_scale /* [n_node] or NULL */,
+                    const float *out_scale /* [n_node] or NULL */, const int32_t *nodes /* [m] or NULL */, int64_t m,
+                    float *out /* [m, n_col] */, double *kernel_ms /* or NULL */);
+int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes /* [m_train] */, const uint32_t *label_bits, int64_t m_train, int32_t n_class,
+                    double alpha, int32_t iters, const float *s /* [n_node] */, const float *a /* [n_node] */,
+                    const int32_t *out_nodes /* [m_out] or NULL */, int64_t m_out, float *F_out /* [m_out, n_class] */,
+                    float *delta /* or NULL */, double *kernel_ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
