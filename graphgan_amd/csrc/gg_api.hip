@@ -288,6 +288,11 @@ int gg::walk_finalize(gg_ctx *ctx, bool *retried) {
             int rc = lazy_fallback_rebuild(ctx, &rebuilt);
             if (rc == GG_ECAPACITY) rc = lazy_rebuild_whole(ctx);  // the arena is full: the whole batch as whole trees
             if (rc != GG_OK) return rc;
+            // The D launch of the step registered its distributions under (slot, rank, has-father), and from the exact part on a
+            // lazy slot's ranks are POOL ranks; in the rebuilt tree the same values name other nodes (the next level in BFS order).
+            // A pending look-up is dropped: the rerun scores privately (dc_valid is cleared below, so no later launch hits either).
+            // A register request stays: the D rerun registers from the rebuilt trees.  (tests/test_gpu_dist_cache.py)
+            if (ctx->dc_request == 2) ctx->dc_request = 0;
             if (ctx->tree_max_depth + 3 > ctx->w_stride) {  // a whole tree may be deeper than the lazy bound
                 ctx->w_stride = ctx->tree_max_depth + 3;
                 GG_HIP(ctx, ctx->w_paths.reserve(sizeof(int32_t) * ((size_t)total * ctx->w_stride + 1)));

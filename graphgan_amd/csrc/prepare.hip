@@ -495,7 +495,10 @@ int gg_prepare_d(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, uint64_t se
         if (rc != GG_OK) return rc;
     }
     bool retried = false;
-    rc = walk_finalize(ctx, &retried);  // the only host synchronisation of the call (a rerun keeps the launch's cache mode)
+    // the only host synchronisation of the call.  A rerun keeps the launch's cache mode when it registers (here: a capacity rerun
+    // and a rerun on rebuilt lazy trees both fill the table anew) and when a look-up launch is rerun for capacity (same trees);
+    // a look-up launch rerun on rebuilt lazy trees drops it (walk_finalize: the ranks it was registered under name other nodes)
+    rc = walk_finalize(ctx, &retried);
     ctx->dc_request = 0;
     if (rc != GG_OK) return rc;
     if (n_slots > 0) {
