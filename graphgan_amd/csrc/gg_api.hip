@@ -385,6 +385,8 @@ int gg_create(int32_t n_node, int32_t n_emb, const float *emb_gen, const float *
     *out = nullptr;
     if (n_node <= 0 || n_emb <= 0 || n_emb > 512 || !emb_gen || !emb_dis || !cfg)
         return fail(nullptr, GG_EINVAL, "gg_create: bad argument (n_node=%d n_emb=%d)", n_node, n_emb);
+    // (a window of 0 or less has no pairs, and hi - lo - 1 of pair_count_kernel would go negative)
+    if (cfg->window_size < 1) return fail(nullptr, GG_EINVAL, "gg_create: window_size = %d is below 1", cfg->window_size);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)

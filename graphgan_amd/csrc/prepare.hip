@@ -431,10 +431,15 @@ __global__ __launch_bounds__(256) void d_fill_kernel(const int32_t *slots, const
     }
 }
 
+// The window the pair kernels and the capacity bounds work with: a path has at most stride - 1 nodes, so no pair is further
+// apart than stride - 2 and every window from `stride` on expands the same pairs.  Clamped, i + window + 1 stays inside an
+// int and the capacity stops growing with a window that no path can use.
+static inline int effective_window(const gg_ctx *ctx, int stride) { return std::min<int>(ctx->cfg.window_size, stride); }
+
 static int fill_g_pairs(gg_ctx *ctx) {
     const int64_t nw = ctx->w_total;
     hipLaunchKernelGGL(pair_fill_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->w_paths.as<int32_t>(),
-                       ctx->w_len.as<int32_t>(), ctx->w_stride, nw, ctx->cfg.window_size, ctx->g_ptr.as<int64_t>(),
+                       ctx->w_len.as<int32_t>(), ctx->w_stride, nw, effective_window(ctx, ctx->w_stride), ctx->g_ptr.as<int64_t>(),
                        ctx->g_node1.as<int32_t>(), ctx->g_node2.as<int32_t>(), ctx->dev_ctr + 3);
     GG_HIP(ctx, hipGetLastError());
     ctx->g_pairs_filled = true;
@@ -533,9 +538,9 @@ int gg_get_d_data(gg_ctx *ctx, int32_t *center, int32_t *neighbor, float *label)
 
 // pairs + rewards of gg_prepare_g behind the walk on the same stream; capacity = bound on pairs
 static int enqueue_g_pairs(gg_ctx *ctx, int64_t nw, int64_t cap) {
-    const int window = ctx->cfg.window_size;
-    hipLaunchKernelGGL(pair_count_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->w_len.as<int32_t>(), nw, window,
-                       ctx->g_cnt.as<int32_t>(), ctx->dev_ctr + 3);
+    const int window = ctx->cfg.window_size;  // (the configured value: it chooses the route; the pair kernels take the clamped one)
+    hipLaunchKernelGGL(pair_count_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, ctx->stream, ctx->w_len.as<int32_t>(), nw,
+                       effective_window(ctx, ctx->w_stride), ctx->g_cnt.as<int32_t>(), ctx->dev_ctr + 3);
     int rc = device_exclusive_scan(ctx, ctx->g_cnt.as<int32_t>(), ctx->g_ptr.as<int64_t>(), nw);
     if (rc != GG_OK) return rc;
     // The (node_1, node_2) arrays are written only for whoever reads them -- gg_get_g_data, minibatch passes, the per-pair
@@ -620,7 +625,7 @@ int gg_prepare_g(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t n_s
     }
     const int64_t nw = ctx->w_total;
     // a path of L = len - 1 <= stride - 1 nodes gives at most 2 * window * L pairs
-    const int64_t cap = nw * 2 * ctx->cfg.window_size * (stride - 1);
+    const int64_t cap = nw * 2 * effective_window(ctx, stride) * (stride - 1);
     if (nw > 0) {
         GG_HIP(ctx, ctx->g_cnt.reserve(sizeof(int32_t) * nw));
         GG_HIP(ctx, ctx->g_ptr.reserve(sizeof(int64_t) * (nw + 1)));
@@ -638,7 +643,7 @@ int gg_prepare_g(gg_ctx *ctx, const int32_t *slots, int32_t n_slots, int32_t n_s
     if (nw > 0) {
         if (retried) {
             // (LAZY trees: slots rebuilt whole may have deepened the paths -- the launch was repeated with a longer stride)
-            const int64_t cap2 = std::max<int64_t>(cap, nw * 2 * ctx->cfg.window_size * (ctx->w_stride - 1));
+            const int64_t cap2 = std::max<int64_t>(cap, nw * 2 * effective_window(ctx, ctx->w_stride) * (ctx->w_stride - 1));
             GG_HIP(ctx, ctx->g_node1.reserve(sizeof(int32_t) * (cap2 + 1)));
             GG_HIP(ctx, ctx->g_node2.reserve(sizeof(int32_t) * (cap2 + 1)));
             GG_HIP(ctx, ctx->g_reward.reserve(sizeof(float) * (cap2 + 1)));

@@ -71,7 +71,9 @@ typedef struct gg_config {
     float adam_beta1;  /* tf.train.AdamOptimizer default 0.9   */
     float adam_beta2;  /* 0.999 */
     float adam_eps;    /* 1e-8  */
-    int32_t window_size; /* config.py:25 */
+    int32_t window_size; /* config.py:25.  >= 1: gg_create refuses anything below with GG_EINVAL.  No upper limit: a path of
+                            L nodes has no pair further apart than L - 1, so every window from the longest path on gives the
+                            same pairs (gg_prepare_g expands with min(window_size, path stride)) */
     int32_t optimizer;   /* GG_OPT_* */
     int32_t device;      /* HIP device ordinal */
     int32_t reserved[6];
