@@ -33,6 +33,8 @@ GRAM_MAX_GRID = 512  # == GRAM_MAX_GRID of csrc/gram.hip: workgroups of a gg_gra
 PAIR_NEIGHBORS_CHUNK = 512  # == PN_CHUNK of csrc/pair_neighbors.hip: a pair whose shorter neighbour list is longer is split into tasks of this many entries
 NEIGHBOR_SUM_CHUNK = 512  # == GP_CHUNK of csrc/graph_prop.hip: a node with more neighbours is split into tasks of this many entries
 NEIGHBOR_SUM_MAX_COL = 128  # == GP_MAX_COL: columns of a neighbour sum / classes of a label spreading at most
+NEIGHBOR_MODE_LDS_CAP = 2048  # == CM_LDS_CAP of csrc/communities.hip: a longer neighbour list is counted in a table in global memory, not in LDS
+PARTITION_EDGES_CHUNK = 512  # == CM_CHUNK: a node with more neighbours is split into tasks of this many entries by gg_partition_edges
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
                GG_ENOMEM: "GG_ENOMEM", GG_EIO: "GG_EIO"}
 
@@ -124,6 +126,9 @@ SIGNATURES = {
     "gg_pair_neighbors": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P, _P]),
     "gg_neighbor_sum": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _i64, _P, _P]),
     "gg_label_spread": (ctypes.c_int, [_P, _P, _P, _i64, _i32, ctypes.c_double, _i32, _P, _P, _P, _i64, _P, _P, _P]),
+    "gg_neighbor_mode": (ctypes.c_int, [_P, _P, _u32, _i32, _P, _i64, _P, _P]),
+    "gg_label_propagation": (ctypes.c_int, [_P, _u32, _i32, _P, _P, _P, _P, _P]),
+    "gg_partition_edges": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
     "gg_pretrain_set_walk_bias": (ctypes.c_int, [_P, _u32, _u32, _u32]),

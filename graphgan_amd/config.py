@@ -138,6 +138,22 @@ engine_lp_heuristics = False
 engine_nc_graph_baseline = False
 engine_lsp_alpha = 0.9          # in (0, 1): the share a node takes from its neighbours
 engine_lsp_iters = 30           # iterations (a label travels one hop per iteration)
+# label-propagation community baseline of node clustering (evaluation/graph_communities.py): with engine_cluster_graph_baseline = True
+# evaluation() appends, under any app, after the graph_nc line and before gen_nll, ONE line "graph_cluster:NMI= ARI= purity= Q=
+# communities= n= iters= converged= seed=" -- label-propagation communities of the WHOLE training graph, detected on the device
+# (gg_label_propagation), the restart with the highest modularity Q kept (seeds engine_seed, engine_seed + 1, ...; the first on ties),
+# scored against the labels over the labelled nodes.  No embedding takes part, so the line is computed at the first evaluation and
+# repeated at every later one: what a community detector on the adjacency lists alone reaches.  Needs labels_filename.  Both defaults
+# are provisional: they have not been tuned on any dataset.
+engine_cluster_graph_baseline = False
+engine_lpa_n_init = 4           # restarts; the highest modularity is kept
+engine_lpa_max_iters = 100      # iterations of a restart at most (it stops at the first one that moves no label)
+# modularity of the clustering lines' partitions (evaluation/graph_communities.py): with engine_cluster_modularity = True (needs
+# engine_node_clustering) evaluation() appends, after the *_sil lines (after the *_cluster lines where there are none), "gen_mod:Q=
+# label_Q= k= n= edges=" and "dis_mod:..." -- Newman's modularity, on the subgraph of the training graph that the labelled nodes induce,
+# of the k-means partition the *_cluster line reports and of the labels taken as the partition (gg_partition_edges): whether the
+# clusters of the embedding are communities of the graph.
+engine_cluster_modularity = False
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

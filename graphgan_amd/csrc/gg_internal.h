@@ -325,6 +325,16 @@ struct gg_ctx {
     int64_t gp_n_stage = 0;
     bool gp_valid = false;
 
+    // gg_neighbor_mode / gg_label_propagation / gg_partition_edges (communities.hip): the all-nodes task plans over the set adjacency --
+    // the neighbour-mode tasks (request rows ordered by class: 4, 16, 64 lanes, the LDS table, the global table; cm_goff: the first
+    // table word of each global-table task) and the (node, first entry) tasks of gg_partition_edges by group width -- functions of
+    // the graph alone: built on first use, dropped by gg_set_graph_csr beside pn_valid; cm_tab holds the global tables of the call
+    // in flight
+    gg::DevBuf cm_task, cm_goff, cm_tab, cm_etask;
+    int64_t cm_first[6] = {}, cm_efirst[4] = {};
+    int64_t cm_tab_words = 0;
+    bool cm_valid = false;
+
     // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
     // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr
     gg::DevBuf gs_es, gs_cpre;

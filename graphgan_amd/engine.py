@@ -16,6 +16,7 @@ from ._lib import GGConfig, GGCounters, check, lib
 from .evaluation.embedding_spectrum import pca_cov, pca_eig
 from .evaluation import link_heuristics as _lheur
 from .evaluation import label_propagation as _lprop
+from .evaluation import graph_communities as _gcomm
 
 
 def _ptr(a):
@@ -699,6 +700,62 @@ class Engine:
         self._ck(lib.gg_label_spread(self._ctx, _ptr(tr), _ptr(bits), len(tr), C, float(alpha), int(iters), _ptr(s), _ptr(a), _ptr(out_a), m_out,
                                      _ptr(F), ctypes.byref(delta), ctypes.byref(ms)))
         return dict(F=F, delta=float(delta.value), ms=ms.value)
+
+    NEIGHBOR_MODE_LDS_CAP = _lib.NEIGHBOR_MODE_LDS_CAP  # neighbours of a node the neighbour-mode sweep counts in an LDS table (a longer list: a table in global memory)
+    PARTITION_EDGES_CHUNK = _lib.PARTITION_EDGES_CHUNK  # neighbours of a node per task of partition_edges (a node with more is split)
+
+    def neighbor_mode(self, labels, salt=0, keep=True, nodes=None):
+        """The neighbour-mode sweep (gg_neighbor_mode) on the neighbour SETS N(v) of the resident training graph (those of
+        ``pair_neighbors``): for v = nodes[i] (``nodes`` None: every node) the most frequent label among labels[w], w in N(v).  A
+        node without neighbours keeps its label; with ``keep`` so does a node whose own label is among the most frequent;
+        otherwise ties go to the label with the smallest pair (fmix32(l ^ salt), l) (evaluation/graph_communities.py).  ``labels``:
+        an int array [n_node], every label >= 0.  All integer: a rerun, a permuted or repeated ``nodes`` and a subset return the
+        same value per node.  No embedding table is read.  Returns dict(out int32 [m], ms)."""
+        fn = "neighbor_mode"
+        lab = _gcomm.check_labels(fn, labels, self.n_node)
+        nodes_a = None if nodes is None else _i32(_lprop.check_nodes(fn, "nodes", nodes, self.n_node))
+        m = self.n_node if nodes_a is None else len(nodes_a)
+        out = np.empty(m, dtype=np.int32)
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_neighbor_mode(self._ctx, _ptr(lab), int(salt) & 0xFFFFFFFF, int(bool(keep)), _ptr(nodes_a), m, _ptr(out), ctypes.byref(ms)))
+        return dict(out=out, ms=ms.value)
+
+    def label_propagation(self, seed=0, max_iters=100):
+        """Label-propagation community detection on the resident training graph (gg_label_propagation;
+        evaluation/graph_communities.py): from L[v] = v, every iteration redraws a split of the nodes into two sides and lets
+        first one side, then the other take ``neighbor_mode(L, keep=True)`` at once; it stops at the first iteration that moves
+        no label or after ``max_iters``.  Labels, the side test and the counters stay on the device; ``T`` iterations equal 2 T
+        ``neighbor_mode`` calls composed on the host, bit for bit.  Returns dict(labels int32 [n_node], iters, converged, changed
+        int64 [iters] -- the labels each iteration moved --, ms)."""
+        fn = "label_propagation"
+        _gcomm.check_max_iters(fn, max_iters)
+        labels = np.empty(self.n_node, dtype=np.int32)
+        changed = np.zeros(int(max_iters), dtype=np.int32)
+        iters, converged, ms = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        self._ck(lib.gg_label_propagation(self._ctx, int(seed) & 0xFFFFFFFF, int(max_iters), _ptr(labels), ctypes.byref(iters), ctypes.byref(converged),
+                                          _ptr(changed), ctypes.byref(ms)))
+        return dict(labels=labels, iters=int(iters.value), converged=bool(converged.value), changed=changed[:iters.value].astype(np.int64), ms=ms.value)
+
+    def partition_edges(self, assign, n_label):
+        """The edge counts of a partition of the resident training graph (gg_partition_edges): ``assign`` an int array [n_node]
+        with a class in [0, n_label) or -1 for "outside the partition"; tot[c] = the ordered pairs (v, w), w in N(v), with v in
+        class c and w inside the partition, intra[c] those with w in class c too.  Exact integers.  Returns dict(intra int64
+        [n_label], tot int64 [n_label], ms)."""
+        a = _gcomm.check_assign("partition_edges", assign, self.n_node, n_label)
+        intra, tot = np.zeros(int(n_label), dtype=np.int64), np.zeros(int(n_label), dtype=np.int64)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_partition_edges(self._ctx, _ptr(a), int(n_label), _ptr(intra), _ptr(tot), ctypes.byref(ms)))
+        return dict(intra=intra, tot=tot, ms=ms.value)
+
+    def modularity(self, assign):
+        """Newman's modularity Q of the partition ``assign`` (classes >= 0, -1: outside; the subgraph the inside nodes induce) on
+        the neighbour sets of the resident training graph: ``graph_communities.modularity_from_counts`` of ``partition_edges``;
+        nan where no edge lies inside."""
+        a = np.asarray(assign)
+        n_label = max(int(a.max()) + 1, 1) if a.size and np.issubdtype(a.dtype, np.integer) else 1
+        res = self.partition_edges(_gcomm.check_assign("modularity", a, self.n_node, n_label), n_label)
+        return _gcomm.modularity_from_counts(res["intra"], res["tot"])
 
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node

@@ -55,6 +55,7 @@ from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
 from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
 from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
 from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
+from graphgan_amd.evaluation import graph_communities as gcomm  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -107,6 +108,20 @@ def _check_nc_graph_baseline(cfg):
                          % (_cfg(cfg, "engine_nc_ml_protocol", "topk"),))
 
 
+def _check_cluster_graph_baseline(cfg):
+    """the label-propagation community line needs the labels file, under any app, at least one restart and one iteration (checked
+    before anything is computed)"""
+    if not _cfg(cfg, "engine_cluster_graph_baseline", False):
+        return
+    path = getattr(cfg, "labels_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("engine_cluster_graph_baseline needs labels: config.labels_filename does not exist (%r)" % (path,))
+    for name, default in (("engine_lpa_n_init", 4), ("engine_lpa_max_iters", 100)):
+        value = _cfg(cfg, name, default)
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (name, value))
+
+
 def _check_link_rank(cfg):
     """the full-ranking lines need the test edges, under any app (checked before anything is computed)"""
     if not _cfg(cfg, "engine_link_rank", False):
@@ -121,6 +136,8 @@ def _check_node_clustering(cfg):
     judge the clustering lines' partition"""
     if _cfg(cfg, "engine_cluster_silhouette", False) and not _cfg(cfg, "engine_node_clustering", False):
         raise ValueError("engine_cluster_silhouette needs engine_node_clustering = True: it scores the k-means partition of the *_cluster lines")
+    if _cfg(cfg, "engine_cluster_modularity", False) and not _cfg(cfg, "engine_node_clustering", False):
+        raise ValueError("engine_cluster_modularity needs engine_node_clustering = True: it scores the k-means partition of the *_cluster lines")
     if not _cfg(cfg, "engine_node_clustering", False):
         return
     path = getattr(cfg, "labels_filename", None)
@@ -171,6 +188,7 @@ class GraphGAN(object):
         _check_node_knn(cfg)
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
+        _check_cluster_graph_baseline(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -190,6 +208,7 @@ class GraphGAN(object):
         self._prepare_no = 0
         self._graph_lp_line = None  # the graph_lp results line (engine_lp_heuristics): a function of the files alone, computed once
         self._graph_nc_line = None  # the graph_nc results line (engine_nc_graph_baseline) likewise
+        self._graph_cluster_line = None  # the graph_cluster results line (engine_cluster_graph_baseline) likewise
 
         self.seed = int(_cfg(cfg, "engine_seed", 0))
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
@@ -555,6 +574,7 @@ class GraphGAN(object):
         _check_node_knn(cfg)
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
+        _check_cluster_graph_baseline(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -627,6 +647,16 @@ class GraphGAN(object):
                                                   max_rows=int(_cfg(cfg, "engine_sil_max_rows", 0)), seed=self.seed)
                     fit = fits[i]
                     results.append(nsil.format_results(cfg.modes[i], nse.eval_node_silhouette(fit["nodes"], fit["classes"], fit["assign"], fit["k"])))
+            if _cfg(cfg, "engine_cluster_modularity", False):
+                # modularity, on the subgraph of the training graph induced by the labelled nodes, of the partitions just reported and
+                # of the labels (gg_partition_edges): one line per mode, "gen_mod:Q=<q> label_Q=<l> k=<k> n=<n> edges=<e>" (without an
+                # engine: the same integers from numpy on the training file, the same string)
+                if self.engine is not None:
+                    edges = gcomm.engine_sweeps(self.engine)[1]
+                else:
+                    edges = gcomm.host_sweeps(utils.read_edges_from_file(cfg.train_filename), self.n_node)[1]
+                for i in range(2):
+                    results.append(gcomm.format_modularity(cfg.modes[i], gcomm.eval_cluster_modularity(edges, self.n_node, fits[i])))
         if _cfg(cfg, "engine_emb_spectrum", False):
             # spectrum of the covariance of the rows of the nodes with a training edge (two gg_gram sweeps, eigh on the host): one
             # line per mode, "gen_spec:erank=<e> pr=<p> top1=<t> top10=<t> var=<v> mean_norm=<n> n=<n> d=<d>" (without an engine: the
@@ -665,6 +695,17 @@ class GraphGAN(object):
                                             multilabel=multilabel)
                 self._graph_nc_line = lprop.format_results(lse.eval_label_spread(), multilabel)
             results.append(self._graph_nc_line)
+        if _cfg(cfg, "engine_cluster_graph_baseline", False):
+            # label-propagation communities of the whole training graph (gg_label_propagation), the restart with the highest
+            # modularity, scored against the labels: ONE line, "graph_cluster:NMI=<n> ARI=<a> purity=<p> Q=<q> communities=<c> n=<n>
+            # iters=<t> converged=<b> seed=<s>" -- computed once and repeated, like graph_lp (without an engine: numpy on the
+            # training file, the same string)
+            if getattr(self, "_graph_cluster_line", None) is None:
+                gce = gcomm.GraphCommunityEval(cfg.train_filename, cfg.labels_filename, self.n_node, engine=self.engine,
+                                               n_init=int(_cfg(cfg, "engine_lpa_n_init", 4)), max_iters=int(_cfg(cfg, "engine_lpa_max_iters", 100)),
+                                               seed=self.seed)
+                self._graph_cluster_line = gcomm.format_results(gce.eval_graph_communities())
+            results.append(self._graph_cluster_line)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

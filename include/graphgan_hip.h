@@ -747,6 +747,70 @@ int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes /* [m_train] */, con
                     const int32_t *out_nodes /* [m_out] or NULL */, int64_t m_out, float *F_out /* [m_out, n_class] */,
                     float *delta /* or NULL */, double *kernel_ms /* or NULL */);
 
+/* ---- neighbour-mode sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * The most frequent neighbour label of every node -- the step of label-propagation community detection (Raghavan et al. 2007) --
+ * the propagation iterated on the device, and the edge counts of a partition from which modularity is one float64 formula.  All
+ * on the set adjacency of the resident training graph: N(v) and deg(v) are those of the pair-neighbour sweep (distinct entries,
+ * no self-loop).  Needs gg_set_graph_csr; no embedding table is read; every result is an integer.
+ *   fmix32      the MurmurHash3 finaliser on uint32, all arithmetic mod 2^32:
+ *               x ^= x >> 16;  x *= 0x85ebca6b;  x ^= x >> 13;  x *= 0xc2b2ae35;  x ^= x >> 16.
+ *
+ * gg_neighbor_mode: labels int32 [n_node], every one >= 0; nodes int32 [m] or NULL for all nodes (m is then not read and out is
+ * [n_node]); with v = nodes[i], cnt(l) = |{w in N(v) : labels[w] == l}| and cmax = max over l of cnt(l):
+ *   deg(v) == 0                          out[i] = labels[v];
+ *   keep != 0 and cnt(labels[v]) == cmax   out[i] = labels[v];
+ *   otherwise                            out[i] = the label l with cnt(l) == cmax that has the smallest pair (fmix32(l ^ salt), l).
+ *   bit contract  integers only and a total order: out for node v is a function of N(v), the labels, salt and keep alone.  A
+ *               rerun, a permuted or repeated `nodes` and a subset return the same value per node.
+ *   shape       by deg(v): up to 64, a group of 4, 16 or 64 lanes (one neighbour per lane, the equal labels counted by broadcast
+ *               and compare, the triples (count descending, hash ascending, label ascending) folded by a shuffle tree); up to
+ *               2048, one workgroup with an open-addressing (label, count) table in LDS of the power of two >= 2 deg(v) slots,
+ *               claimed by compare-and-swap and counted by integer adds; above, the same on a zeroed table in global memory from
+ *               a scratch buffer of the context.  No list is truncated; no path depends on the number of distinct labels.  The
+ *               task plan of the all-nodes sweep is built once per graph and dropped by gg_set_graph_csr.
+ *   limits      m >= 0 (m == 0 succeeds and writes nothing); labels and out not NULL; labels >= 0; ids in [0, n_node); a resident
+ *               graph.  Anything else: GG_EINVAL with the texts
+ *                 "gg_neighbor_mode: needs the training graph (gg_set_graph_csr)", "gg_neighbor_mode: m = <m> is negative",
+ *                 "gg_neighbor_mode: labels and out must not be NULL", "gg_neighbor_mode: labels[<v>] = <l> is negative" (the FIRST
+ *                 offender), "gg_neighbor_mode: nodes[<i>] = <id> out of range [0, <n_node>)" (the FIRST bad index);
+ *               nothing is launched.
+ *
+ * gg_label_propagation: from L[v] = v, iterations t = 1, 2, ...:
+ *   st = fmix32((seed ^ 0x85ebca6b) + 0x9E3779B9 * t),   side(v) = fmix32(v ^ st) & 1;
+ *   half-step h = 0, then h = 1: the nodes with side(v) == h take gg_neighbor_mode(L, salt = fmix32(seed + 0x9E3779B9 *
+ *   (2 (t - 1) + h + 1)), keep = 1) all at once, every other node keeps its label;
+ *   changed[t - 1] = the number of labels the two half-steps moved; stop at the first t with changed == 0 (*converged = 1) or
+ *   after max_iters (*converged = 0); *iters = t, labels = L.  The split is redrawn every iteration: with a fixed split pairs of
+ *   nodes on one side keep swapping labels for ever.
+ *   residency   L, the side test and the changed words stay on the device for the whole call; one 4-byte count per iteration
+ *               crosses to the host.  The half-steps run the kernels of gg_neighbor_mode (the side is an argument), so T
+ *               iterations equal 2 T calls of gg_neighbor_mode composed on the host, bit for bit.
+ *   limits      max_iters >= 1 ("gg_label_propagation: max_iters = <k> is below 1"); labels, iters, converged and changed
+ *               (int32 [max_iters]; entries behind *iters are not written) not NULL ("gg_label_propagation: labels, iters,
+ *               converged and changed must not be NULL"); a resident graph ("gg_label_propagation: needs the training graph
+ *               (gg_set_graph_csr)").
+ *
+ * gg_partition_edges: assign int32 [n_node], assign[v] in [0, n_label) or -1 for "outside the partition";
+ *   tot[c]   = sum over v with assign[v] == c of |{w in N(v) : assign[w] >= 0}|,
+ *   intra[c] = sum over v with assign[v] == c of |{w in N(v) : assign[w] == c}|   (ordered pairs: an inner edge counts twice).
+ *   With M2 = sum of tot, modularity is Q = sum over c of (intra[c] / M2 - (tot[c] / M2)^2) -- computed by the caller in float64.
+ *   shape       groups of 4, 16 or 64 lanes per node (deg <= 8, <= 64, above), a list longer than 512 entries split into tasks
+ *               of 512.  A group's first lane holds the counts of its tasks while their class stays the same, and the lanes of a
+ *               wavefront that add into one class add through one lane: unsigned 64-bit atomic adds, exact whatever the order,
+ *               and few of them where the partition has few classes.
+ *   limits      n_label >= 1 ("gg_partition_edges: n_label = <k> is below 1"); assign, intra and tot not NULL
+ *               ("gg_partition_edges: assign, intra and tot must not be NULL"); "gg_partition_edges: assign[<v>] = <a> outside
+ *               [-1, <n_label>)" (the FIRST offender); "gg_partition_edges: needs the training graph (gg_set_graph_csr)".
+ * kernel_ms (may be NULL): HIP-event time on the context's stream -- of the sweep kernels (gg_neighbor_mode, gg_partition_edges)
+ * or of the whole fit with its per-iteration read-backs (gg_label_propagation).  Temporary device buffers are freed on every
+ * exit path. */
+int gg_neighbor_mode(gg_ctx *ctx, const int32_t *labels /* [n_node] */, uint32_t salt, int32_t keep, const int32_t *nodes /* [m] or NULL */,
+                     int64_t m, int32_t *out /* [m] */, double *kernel_ms /* or NULL */);
+int gg_label_propagation(gg_ctx *ctx, uint32_t seed, int32_t max_iters, int32_t *labels /* [n_node] */, int32_t *iters, int32_t *converged,
+                         int32_t *changed /* [max_iters] */, double *kernel_ms /* or NULL */);
+int gg_partition_edges(gg_ctx *ctx, const int32_t *assign /* [n_node] */, int32_t n_label, int64_t *intra /* [n_label] */,
+                       int64_t *tot /* [n_label] */, double *kernel_ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
