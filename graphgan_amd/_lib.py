@@ -34,6 +34,7 @@ PAIR_NEIGHBORS_CHUNK = 512  # == PN_CHUNK of csrc/pair_neighbors.hip: a pair who
 NEIGHBOR_SUM_CHUNK = 512  # == GP_CHUNK of csrc/graph_prop.hip: a node with more neighbours is split into tasks of this many entries
 NEIGHBOR_SUM_MAX_COL = 128  # == GP_MAX_COL: columns of a neighbour sum / classes of a label spreading at most
 NEIGHBOR_MODE_LDS_CAP = 2048  # == CM_LDS_CAP of csrc/communities.hip: a longer neighbour list is counted in a table in global memory, not in LDS
+TWO_HOP_LDS_CAP = 2048  # == TH_LDS_CAP of csrc/two_hop.hip: a query with more expansion entries accumulates in a table in global memory, not in LDS
 PARTITION_EDGES_CHUNK = 512  # == CM_CHUNK: a node with more neighbours is split into tasks of this many entries by gg_partition_edges
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
                GG_ENOMEM: "GG_ENOMEM", GG_EIO: "GG_EIO"}
@@ -129,6 +130,8 @@ SIGNATURES = {
     "gg_neighbor_mode": (ctypes.c_int, [_P, _P, _u32, _i32, _P, _i64, _P, _P]),
     "gg_label_propagation": (ctypes.c_int, [_P, _u32, _i32, _P, _P, _P, _P, _P]),
     "gg_partition_edges": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P]),
+    "gg_two_hop_topk": (ctypes.c_int, [_P, _P, _i64, _i32, _P, _i32, _i64, _P, _P, _P, _P]),
+    "gg_two_hop_rank": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _i64, _P, _P, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
     "gg_pretrain_set_walk_bias": (ctypes.c_int, [_P, _u32, _u32, _u32]),

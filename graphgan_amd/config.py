@@ -154,6 +154,17 @@ engine_lpa_max_iters = 100      # iterations of a restart at most (it stops at t
 # of the k-means partition the *_cluster line reports and of the labels taken as the partition (gg_partition_edges): whether the
 # clusters of the embedding are communities of the graph.
 engine_cluster_modularity = False
+# graph-only ranking baselines (evaluation/graph_ranking.py): what ranking every node by a neighbourhood index on the training graph
+# alone -- the two-hop sweep, gg_two_hop_rank / gg_two_hop_topk; no embedding takes part -- reaches on the two ranking evaluators.  Both
+# knobs work under any app, need test_filename, and write one line per index of engine_graph_rank_indices, after the graph_cluster line
+# and before gen_nll; the lines are computed at the first evaluation and repeated at every later one.
+#   engine_link_rank_graph_baseline   "graph_rank:index=<i> MRR= MR= H@<K>= ... n= reach=": the queries, the filter and the K
+#                                     (engine_link_rank_ks) of the *_rank lines; reach: the share of queries whose target scores > 0
+#   engine_rec_graph_baseline         "graph_rec:index=<i> P@<K>= R@<K>= ...": the queries, the scoring and the K (engine_rec_ks) of
+#                                     the app = "recommendation" lines
+engine_link_rank_graph_baseline = False
+engine_rec_graph_baseline = False
+engine_graph_rank_indices = ("cn", "aa", "ra")   # common neighbours, Adamic-Adar, resource allocation
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

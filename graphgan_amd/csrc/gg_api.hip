@@ -529,7 +529,7 @@ int gg_destroy(gg_ctx *ctx) {
                       &ctx->step_u, &ctx->step_v, &ctx->step_x, &ctx->sg_rows, &ctx->sg_bias, &ctx->touched_ptr, &ctx->x_cnt, &ctx->x_send_ids, &ctx->x_send_rows,
                       &ctx->x_recv_ids, &ctx->x_recv_rows, &ctx->x_nglob, &ctx->x_own, &ctx->st_item, &ctx->st_item2, &ctx->st_cur, &ctx->st_prev, &ctx->st_len,
                       &ctx->st_alive, &ctx->st_rank, &ctx->bfs_key, &ctx->bfs_bm, &ctx->bfs_misc, &ctx->bfs_sparse, &ctx->bfs_rowptr32, &ctx->lv_pfx, &ctx->dc_keys, &ctx->dc_vals, &ctx->dc_words, &ctx->lv_beg, &ctx->lv_k, &ctx->lv_chunks, &ctx->lv_coff, &ctx->lv_scores, &ctx->lv_chunk_owner, &ctx->lv_prefix, &ctx->lv_big, &ctx->lv_fe, &ctx->fin_list, &ctx->table_bad, &ctx->hub_acc,
-                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj, &ctx->pn_ptr, &ctx->pn_adj, &ctx->gp_task, &ctx->gp_hub, &ctx->gp_stage, &ctx->cm_task, &ctx->cm_goff, &ctx->cm_tab, &ctx->cm_etask,
+                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj, &ctx->pn_ptr, &ctx->pn_adj, &ctx->gp_task, &ctx->gp_hub, &ctx->gp_stage, &ctx->cm_task, &ctx->cm_goff, &ctx->cm_tab, &ctx->cm_etask, &ctx->th_tab,
                       &ctx->gs_es, &ctx->gs_cpre, &ctx->pt_starts, &ctx->pt_paths, &ctx->pt_len, &ctx->pt_cnt, &ctx->pt_ptr, &ctx->pt_noise, &ctx->pt_sample};
     for (DevBuf *b : bufs) b->release();
     for (StageIndex *ix : {&ctx->sg_own, &ctx->sg_early}) ix->release();

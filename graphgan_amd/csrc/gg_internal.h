@@ -314,6 +314,7 @@ struct gg_ctx {
     // first use; dropped by gg_set_graph_csr
     gg::DevBuf pn_ptr, pn_adj;
     std::vector<int64_t> h_pn_ptr;
+    std::vector<int32_t> h_pn_adj;  // host copy of the lists (the two-hop sweep plans from it)
     int32_t pn_max_deg = 0;
     bool pn_valid = false;
 
@@ -334,6 +335,10 @@ struct gg_ctx {
     int64_t cm_first[6] = {}, cm_efirst[4] = {};
     int64_t cm_tab_words = 0;
     bool cm_valid = false;
+
+    // gg_two_hop_topk / gg_two_hop_rank (two_hop.hip): the zeroed (column, uint64 sum) tables of the global-table queries of the pass in
+    // flight; the task plan is per call, so gg_set_graph_csr drops nothing
+    gg::DevBuf th_tab;
 
     // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
     // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr

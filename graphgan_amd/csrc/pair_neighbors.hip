@@ -148,6 +148,8 @@ int ensure_set_adjacency(gg_ctx *ctx) {
     if (e == hipSuccess) e = hipMemcpy(ctx->pn_ptr.p, ptr.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess && total) e = hipMemcpy(ctx->pn_adj.p, s.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "set adjacency (%lld entries): %s", (long long)total, hipGetErrorString(e));
+    s.resize(total);
+    ctx->h_pn_adj.swap(s);  // (the host copy of the lists: the two-hop sweep plans its queries from it, two_hop.hip)
     ctx->pn_max_deg = (int32_t)max_deg;
     ctx->pn_valid = true;
     return GG_OK;

@@ -17,6 +17,7 @@ from .evaluation.embedding_spectrum import pca_cov, pca_eig
 from .evaluation import link_heuristics as _lheur
 from .evaluation import label_propagation as _lprop
 from .evaluation import graph_communities as _gcomm
+from .evaluation import graph_ranking as _grank
 
 
 def _ptr(a):
@@ -193,6 +194,8 @@ class Engine:
         self.tree_roots = np.zeros(0, dtype=np.int32)
         self.max_depth = 0
         self._rowptr = None
+        self._col = None
+        self._set_adj = None
         self.tree_mode = (-1, 0)  # (mode, node_cap) of the last set_tree_mode: the library's default until then
         self.last_graph_softmax_ms = 0.0
 
@@ -217,6 +220,8 @@ class Engine:
         col = _i32(col)
         self._ck(lib.gg_set_graph_csr(self._ctx, _ptr(rowptr), _ptr(col)))
         self._rowptr = rowptr
+        self._col = col
+        self._set_adj = None  # (the neighbour sets on the host, built when two_hop_rank first derives a full rank)
 
     def build_trees(self, roots, n_threads=0, device=False):
         """graph_gan.py:31-46,84-108: BFS trees of ``roots`` -> device tree CSR (slot i = roots[i]).
@@ -756,6 +761,62 @@ class Engine:
         n_label = max(int(a.max()) + 1, 1) if a.size and np.issubdtype(a.dtype, np.integer) else 1
         res = self.partition_edges(_gcomm.check_assign("modularity", a, self.n_node, n_label), n_label)
         return _gcomm.modularity_from_counts(res["intra"], res["tot"])
+
+    TWO_HOP_LDS_CAP = _lib.TWO_HOP_LDS_CAP  # expansion entries of a query the two-hop sweep accumulates in an LDS table (more: a table in global memory)
+
+    def _two_hop_args(self, fn, weights, exclude, scratch_bytes):
+        return _grank.check_weights(fn, weights, self.n_node), _grank.check_exclude(fn, exclude), _grank.check_scratch(fn, scratch_bytes)
+
+    def two_hop_topk(self, rows, k=10, weights=None, exclude=True, scratch_bytes=None):
+        """The two-hop sweep's lists (gg_two_hop_topk; evaluation/graph_ranking.py): for each query node rows[i] the first ``k``
+        (<= 256) eligible candidates c with S(u, c) > 0, S(u, c) = sum over w in N(u) & N(c) of weights[w] on the neighbour SETS
+        of the resident training graph (those of ``pair_neighbors``: S is its ``cn`` / ``wsum``), score descending, column
+        ascending.  ``weights``: None (every weight 1: common neighbours) or [n_node] non-negative integers, summed as unsigned
+        64-bit integers (max(weights) * max(deg) must fit in 63 bits).  ``exclude``: True -- without u and its training
+        neighbours, the candidates of ``topk(exclude=True)`` -- or "self" -- without u alone; False is refused.  ``scratch_bytes``:
+        the cap on the global-memory tables of one internal pass (None: the default); results do not depend on it.  All integer: a
+        rerun and permuted, repeated or subset queries return the same bits per query.  No embedding table is read.
+        Returns dict(col int32 [m, k] padded with -1, score uint64 [m, k] padded with 0, n_pos int32 [m] = the eligible candidates
+        with S > 0, which may exceed k, ms)."""
+        fn = "two_hop_topk"
+        w, code, scratch = self._two_hop_args(fn, weights, exclude, scratch_bytes)
+        k = _grank.check_k(fn, k)
+        rows_a = _i32(_grank.check_ids(fn, "rows", rows, self.n_node))
+        m = len(rows_a)
+        col = np.full((m, k), -1, dtype=np.int32)
+        score = np.zeros((m, k), dtype=np.uint64)
+        n_pos = np.zeros(m, dtype=np.int32)
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_two_hop_topk(self._ctx, _ptr(rows_a), m, k, _ptr(w), code, scratch, _ptr(col), _ptr(score), _ptr(n_pos), ctypes.byref(ms)))
+        return dict(col=col, score=score, n_pos=n_pos, ms=ms.value)
+
+    def two_hop_rank(self, u, v, weights=None, exclude=True, scratch_bytes=None):
+        """The two-hop sweep's ranks (gg_two_hop_rank; evaluation/graph_ranking.py): for each query (u[i], v[i]) the position of
+        v in ``two_hop_topk``'s order of row u over ALL candidates -- the eligible nodes and always the target itself, the
+        contract of ``rank``.  The device counts, over the eligible c != v with S(u, c) > 0, n_pos (all of them), ahead (those
+        before v in the order) and pos_below (those with c < v); ``graph_ranking.full_rank`` places a zero-score target among
+        the zero-score nodes without visiting them.  With an eligible target and score > 0, rank <= k holds exactly when
+        ``two_hop_topk`` lists v at position rank - 1.  Returns dict(rank int64 [m] (1 = best), n_cand int64 [m], score uint64 [m]
+        = S(u, v), ahead int32 [m], n_pos int32 [m], pos_below int32 [m], ms)."""
+        fn = "two_hop_rank"
+        w, code, scratch = self._two_hop_args(fn, weights, exclude, scratch_bytes)
+        u_a, v_a = _i32(_grank.check_ids(fn, "u", u, self.n_node)), _i32(_grank.check_ids(fn, "v", v, self.n_node))
+        if len(u_a) != len(v_a):
+            raise ValueError("%s: u and v must have the same length, got %d and %d" % (fn, len(u_a), len(v_a)))
+        m = len(u_a)
+        score = np.zeros(m, dtype=np.uint64)
+        ahead, n_pos, pos_below = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_two_hop_rank(self._ctx, _ptr(u_a), _ptr(v_a), m, _ptr(w), code, scratch, _ptr(score), _ptr(ahead), _ptr(n_pos), _ptr(pos_below),
+                                         ctypes.byref(ms)))
+        else:
+            return dict(rank=np.zeros(0, dtype=np.int64), n_cand=np.zeros(0, dtype=np.int64), score=score, ahead=ahead, n_pos=n_pos, pos_below=pos_below, ms=0.0)
+        if self._set_adj is None:
+            self._set_adj = _lheur.csr_set_adjacency(self._rowptr, self._col)
+        rank, n_cand = _grank.full_rank(self._set_adj[0], self._set_adj[1], u_a, v_a, code, score, ahead, n_pos, pos_below)
+        return dict(rank=rank, n_cand=n_cand, score=score, ahead=ahead, n_pos=n_pos, pos_below=pos_below, ms=ms.value)
 
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node

@@ -56,6 +56,7 @@ from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
 from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
 from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
 from graphgan_amd.evaluation import graph_communities as gcomm  # noqa: E402
+from graphgan_amd.evaluation import graph_ranking as grank  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -120,6 +121,19 @@ def _check_cluster_graph_baseline(cfg):
         value = _cfg(cfg, name, default)
         if isinstance(value, bool) or not isinstance(value, int) or value < 1:
             raise ValueError("%s must be an integer >= 1, got %r" % (name, value))
+
+
+def _check_graph_ranking(cfg):
+    """the graph-only ranking lines need the test edges, under any app, known indices and the K of their evaluators (checked before
+    anything is computed)"""
+    for knob, ks_name, ks_default, cls in (("engine_link_rank_graph_baseline", "engine_link_rank_ks", lrank.DEFAULT_KS, grank.GraphRankEval),
+                                           ("engine_rec_graph_baseline", "engine_rec_ks", (2, 10, 20), grank.GraphRecEval)):
+        if not _cfg(cfg, knob, False):
+            continue
+        path = getattr(cfg, "test_filename", None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("%s needs test edges: config.test_filename does not exist (%r)" % (knob, path))
+        cls(cfg.train_filename, path, 1, indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES), ks=tuple(_cfg(cfg, ks_name, ks_default)))
 
 
 def _check_link_rank(cfg):
@@ -189,6 +203,7 @@ class GraphGAN(object):
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
         _check_cluster_graph_baseline(cfg)
+        _check_graph_ranking(cfg)
         test_filename = cfg.test_filename
         if cfg.app == "node_classification" and not os.path.isfile(test_filename):
             test_filename = ""  # the app has no test edges
@@ -209,6 +224,8 @@ class GraphGAN(object):
         self._graph_lp_line = None  # the graph_lp results line (engine_lp_heuristics): a function of the files alone, computed once
         self._graph_nc_line = None  # the graph_nc results line (engine_nc_graph_baseline) likewise
         self._graph_cluster_line = None  # the graph_cluster results line (engine_cluster_graph_baseline) likewise
+        self._graph_rank_lines = None  # the graph_rank / graph_rec results lines (engine_link_rank_graph_baseline, engine_rec_graph_baseline) likewise
+        self._graph_rec_lines = None
 
         self.seed = int(_cfg(cfg, "engine_seed", 0))
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
@@ -575,6 +592,7 @@ class GraphGAN(object):
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
         _check_cluster_graph_baseline(cfg)
+        _check_graph_ranking(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -706,6 +724,21 @@ class GraphGAN(object):
                                                seed=self.seed)
                 self._graph_cluster_line = gcomm.format_results(gce.eval_graph_communities())
             results.append(self._graph_cluster_line)
+        if _cfg(cfg, "engine_link_rank_graph_baseline", False) or _cfg(cfg, "engine_rec_graph_baseline", False):
+            # the ranking evaluators' graph-only lines (gg_two_hop_rank / gg_two_hop_topk): per index of engine_graph_rank_indices,
+            # "graph_rank:index=<i> MRR=<m> MR=<r> H@1=<h> ... n=<n> reach=<r>" and "graph_rec:index=<i> P@2=<p> R@2=<r> ..." --
+            # computed once and repeated, like graph_lp (without an engine: numpy on the training file, the same strings)
+            kw = dict(engine=self.engine, indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES))
+            if _cfg(cfg, "engine_link_rank_graph_baseline", False):
+                if getattr(self, "_graph_rank_lines", None) is None:
+                    self._graph_rank_lines = grank.GraphRankEval(cfg.train_filename, cfg.test_filename, self.n_node,
+                                                                 ks=tuple(_cfg(cfg, "engine_link_rank_ks", lrank.DEFAULT_KS)), **kw).lines()
+                results.extend(self._graph_rank_lines)
+            if _cfg(cfg, "engine_rec_graph_baseline", False):
+                if getattr(self, "_graph_rec_lines", None) is None:
+                    self._graph_rec_lines = grank.GraphRecEval(cfg.train_filename, cfg.test_filename, self.n_node,
+                                                               ks=tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20))), **kw).lines()
+                results.extend(self._graph_rec_lines)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -811,6 +811,65 @@ int gg_label_propagation(gg_ctx *ctx, uint32_t seed, int32_t max_iters, int32_t 
 int gg_partition_edges(gg_ctx *ctx, const int32_t *assign /* [n_node] */, int32_t n_label, int64_t *intra /* [n_label] */,
                        int64_t *tot /* [n_label] */, double *kernel_ms /* or NULL */);
 
+/* ---- two-hop sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * Per query node u one row of A W A on the set adjacency of the resident training graph -- N(x) and deg(x) are those of the
+ * pair-neighbour sweep (distinct entries, no self-loop) -- and from it the best k candidates or the place of one target: the
+ * graph-only baseline of the ranking evaluators (gg_topk_scores / gg_rank_scores on the embedding side), and "friends of friends"
+ * recommendation from an edge list.  Needs gg_set_graph_csr; no embedding table is read; every result is an integer.
+ *   score       S(u, c) = sum over w in N(u) & N(c) of weights[w], unsigned 64-bit; weights uint64 [n_node] or NULL = every weight
+ *               1 (common neighbours).  S(u, c) equals the cn / wsum of gg_pair_neighbors for the pair (u, c), also at c == u,
+ *               where S = the sum over N(u).  max(weights) * max(deg) must fit in 63 bits (checked on the host).
+ *   eligibility exclude = 1 ("self"): every c != u;  exclude = 2 ("graph"): every c outside N(u) + {u} -- the candidates of
+ *               gg_topk_scores with exclude = 1.
+ *   order       score descending, column ascending (the order of gg_topk_scores / gg_rank_scores).
+ *
+ * gg_two_hop_topk: rows int32 [n_rows], ids may repeat; 1 <= k <= 256.  Row i of out_col / out_score [n_rows, k] gets the first k
+ * eligible candidates with S > 0 in that order, padded with col = -1, score = 0; n_pos[i] = the number of eligible candidates with
+ * S > 0 (it may exceed k).  Zero-score nodes never enter a list: they would fill it by node id.
+ *
+ * gg_two_hop_rank: queries (u[i], v[i]), i < m.  The target v is always a candidate, also where the exclusion rule would drop it
+ * (the contract of gg_rank_scores).  Over the eligible c != v:
+ *   score[i]     = S(u, v);
+ *   n_pos[i]     = |{c : S(u, c) > 0}|;
+ *   ahead[i]     = |{c : S(u, c) > 0 and (S(u, c) > S(u, v) or (S(u, c) == S(u, v) and c < v))}|;
+ *   pos_below[i] = |{c : S(u, c) > 0 and c < v}|.
+ * The position of v among ALL its candidates follows on the host (graphgan_amd/evaluation/graph_ranking.py: full_rank, the one
+ * function of the device and the host path): rank = 1 + ahead if score > 0, else 1 + n_pos + (E_below - pos_below), E_below = the
+ * eligible c < v = v minus the ids below v in excl(u) \ {v}; n_cand = n_node - |excl(u) \ {v}|.  The zero-score nodes are never
+ * visited.  With an eligible target and score > 0, rank <= k holds exactly when gg_two_hop_topk lists v at position rank - 1 with
+ * the same score.
+ *
+ *   bit contract  integers only and a total order: a query's outputs are a function of the graph, the weights, exclude and the
+ *               query alone.  A rerun, permuted, repeated or subset queries and any scratch_bytes return the same bits per query.
+ *   shape       the host plans per query T(u) = sum over w in N(u) of deg(w), the entries of the expansion.  One workgroup per
+ *               query fills an open-addressing (column, uint64 sum) table of the power of two >= 2 min(T, n_node) slots (at least
+ *               256): slots claimed by compare-and-swap, values added with 64-bit integer atomics, linear probing from column mod
+ *               slots.  T <= 2048: the table lies in LDS; above, in a zeroed table of a scratch buffer of the context.  Lists
+ *               N(w) of up to 64 entries are walked by groups of 16 lanes, longer ones by the whole workgroup: no list is
+ *               truncated.  Then one scan of the table: for the rank, counts by compares against the target's entry; for the
+ *               lists, a radix select on the composite key (score, ~column), 8 bits per pass, and a bitonic sort of the
+ *               survivors.  Eligibility under exclude = 2 is a binary search in the sorted N(u).
+ *   scratch_bytes  the cap on the global-memory tables of one internal pass; 0 = the default (256 MiB).  Queries whose tables do
+ *               not fit together run in several passes; a pass holds at least one query whatever its table's size.
+ *   limits      n_rows, m >= 0 (0 succeeds and writes nothing) and below 2^31; ids in [0, n_node); a resident graph.  Anything
+ *               else: GG_EINVAL with the texts (<fn> = the entry point's name, <m> = "n_rows" or "m")
+ *                 "<fn>: needs the training graph (gg_set_graph_csr)", "<fn>: <m> = <value> is negative",
+ *                 "<fn>: <m> = <value> does not fit in 31 bits", "<fn>: exclude = <e> is neither 1 (self) nor 2 (graph)",
+ *                 "<fn>: scratch_bytes = <b> is negative", "gg_two_hop_topk: k = <k> outside [1, 256]",
+ *                 "gg_two_hop_topk: rows, out_col, out_score and n_pos must not be NULL",
+ *                 "gg_two_hop_rank: u, v, score, ahead, n_pos and pos_below must not be NULL",
+ *                 "<fn>: rows[<i>] = <id> out of range [0, <n_node>)" (likewise u, then v; the FIRST bad index),
+ *                 "<fn>: the largest weight <w> times the largest degree <d> does not fit in 63 bits";
+ *               nothing is launched.
+ * kernel_ms (may be NULL): HIP-event time of the sweep kernels and the table clears on the context's stream, summed over the
+ * internal passes.  Temporary device buffers are freed on every exit path. */
+int gg_two_hop_topk(gg_ctx *ctx, const int32_t *rows /* [n_rows] */, int64_t n_rows, int32_t k, const uint64_t *weights /* [n_node] or NULL */,
+                    int32_t exclude, int64_t scratch_bytes, int32_t *out_col /* [n_rows, k] */, uint64_t *out_score /* [n_rows, k] */,
+                    int32_t *n_pos /* [n_rows] */, double *kernel_ms /* or NULL */);
+int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u /* [m] */, const int32_t *v /* [m] */, int64_t m, const uint64_t *weights /* [n_node] or NULL */,
+                    int32_t exclude, int64_t scratch_bytes, uint64_t *score /* [m] */, int32_t *ahead /* [m] */, int32_t *n_pos /* [m] */,
+                    int32_t *pos_below /* [m] */, double *kernel_ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
