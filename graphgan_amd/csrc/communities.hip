@@ -8,19 +8,18 @@
 //   d <= 64     a group of W = 4, 16 or 64 lanes per node (the smallest that holds the list): each lane gathers one neighbour's
 //               label, counts the equal labels of its group by broadcast and compare, and the group folds the triples
 //               (count descending, fmix32(l ^ salt) ascending, l ascending) by a shuffle tree;
-//   d <= 2048   one workgroup per node fills an open-addressing (label + 1, count) table in LDS of T = the power of two
-//               >= 2 d slots (CM_LDS_CAP = 2048 entries -> 4096 slots, 32 KiB: five workgroups share a CU's 160 KiB): a slot is
-//               claimed by compare-and-swap and counted by an LDS integer add, linear probing from l mod T; then the
-//               workgroup scans the table for the best triple and for the count of the node's own label;
-//   d > 2048    the same on a zeroed table in global memory, T slots from the context's scratch buffer per task (global
-//               compare-and-swap and adds, read back with device-scope loads).
+//   d <= 2048   one workgroup per node counts the labels in a (label, uint32 count) SetTable (set_sweep.h) in LDS
+//               (CM_LDS_CAP = 2048 entries -> 4096 slots, 32 KiB: five workgroups share a CU's 160 KiB), then scans the table
+//               for the best triple and for the count of the node's own label;
+//   d > 2048    the same on a zeroed table in global memory, per task T key words and then T count words of the context's
+//               scratch buffer.
 // No list is truncated and no path depends on how many distinct labels occur.  Counts are integers and the fold is a total
 // order on (count, hash, label), so a node's result depends on its list and the labels alone -- not on the request, the grid,
 // the order of the inserts or the run.  The side test of label propagation is an ARGUMENT of the one set of kernels (side_h),
 // so T iterations of gg_label_propagation equal 2 T calls of gg_neighbor_mode composed on the host, bit for bit.
 #include <algorithm>
 
-#include "gg_internal.h"
+#include "set_sweep.h"
 
 namespace gg {
 
@@ -126,30 +125,19 @@ __global__ __launch_bounds__(256) void cm_mode_table_kernel(CmArgs o) {
         }
         const int64_t b0 = o.ptr[v];
         const int d = (int)(o.ptr[v + 1] - b0);
-        uint32_t T = 256;
-        while (T < 2u * (uint32_t)d) T <<= 1;  // (d < 2^31 and, on the LDS path, d <= CM_LDS_CAP: T <= CM_LDS_SLOTS)
-        uint32_t *key = GLOBAL ? o.tab + o.goff[t] : s_key, *cnt = GLOBAL ? key + T : s_cnt;
-        if (!GLOBAL) {
-            for (uint32_t s = tid; s < T; s += 256) s_key[s] = 0u, s_cnt[s] = 0u;
-            __syncthreads();
-        }
-        for (int e = tid; e < d; e += 256) {
-            const uint32_t k = (uint32_t)o.labels[o.adj[b0 + e]] + 1u;  // 0 marks an empty slot
-            uint32_t s = (k - 1u) & (T - 1u);
-            for (;;) {  // at most d distinct labels in T >= 2 d slots: a free or matching slot is always met
-                const uint32_t old = atomicCAS(key + s, 0u, k);
-                if (old == 0u || old == k) break;
-                s = (s + 1u) & (T - 1u);
-            }
-            atomicAdd(cnt + s, 1u);
-        }
-        if (GLOBAL) __threadfence();
-        __syncthreads();
+        const uint32_t T = set_table_slots((uint32_t)d);  // (d <= 2^30 and, on the LDS path, d <= CM_LDS_CAP: T <= CM_LDS_SLOTS)
+        SetTable<uint32_t, GLOBAL> tb;  // at most d distinct labels
+        tb.key = GLOBAL ? o.tab + o.goff[t] : s_key;
+        tb.val = GLOBAL ? tb.key + T : s_cnt;
+        tb.mask = T - 1u;
+        if (!GLOBAL) tb.clear_lds();
+        for (int e = tid; e < d; e += 256) tb.add(o.labels[o.adj[b0 + e]], 1u);
+        tb.fill_done();
         uint32_t c = 0, h = 0xffffffffu, l = 0xffffffffu, own_c = 0;
         for (uint32_t s = tid; s < T; s += 256) {
-            const uint32_t k = GLOBAL ? __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : key[s];
+            const uint32_t k = tb.ld_key(s);
             if (k == 0u) continue;
-            const uint32_t c2 = GLOBAL ? __hip_atomic_load(cnt + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : cnt[s];
+            const uint32_t c2 = tb.ld_val(s);
             const uint32_t l2 = k - 1u, h2 = fmix32(l2 ^ o.salt);
             if (l2 == (uint32_t)own) own_c = c2;
             if (cm_better(c2, h2, l2, c, h, l)) c = c2, h = h2, l = l2;
@@ -255,14 +243,9 @@ __global__ __launch_bounds__(256) void cm_edges_kernel(CeArgs o) {
 
 int mode_class(int64_t d) { return d <= 4 ? 0 : d <= 16 ? 1 : d <= 64 ? 2 : d <= CM_LDS_CAP ? 3 : 4; }
 
-int64_t table_slots(int64_t d) {
-    int64_t T = 256;
-    while (T < 2 * d) T <<= 1;
-    return T;
-}
-
 // The tasks of a neighbour-mode request, ordered by class; the global tables of the giant lists, one per TASK (a repeated node
-// has one per occurrence).
+// has one per occurrence).  (Not set_sweep.h's planner: five classes of whole rows, and the table offsets come out of the fill.)
+static_assert(sizeof(DevModePlan::first) == sizeof(int64_t) * (CM_CLASSES + 1), "DevModePlan holds the classes' first tasks");
 struct ModePlan {
     std::vector<int32_t> task;
     std::vector<int64_t> goff;
@@ -286,23 +269,16 @@ void build_mode_plan(const int64_t *hp, const int32_t *nodes, int64_t m, ModePla
         const int c = mode_class(d);
         if (c == 4) {
             p.goff[(size_t)(fill[4] - p.first[4])] = p.tab_words;
-            p.tab_words += 2 * table_slots(d);
+            p.tab_words += 2 * set_table_slots(d);
         }
         p.task[(size_t)fill[c]++] = (int32_t)i;
     }
 }
 
-struct DevModePlan {
-    const int32_t *task = nullptr;
-    const int64_t *goff = nullptr;
-    int64_t first[CM_CLASSES + 1] = {};
-    int64_t tab_words = 0;
-};
-
 int upload_mode_plan(gg_ctx *ctx, const char *fn, const ModePlan &p, DevBuf &d_task, DevBuf &d_goff, DevModePlan &dp) {
     hipError_t e = d_task.reserve(sizeof(int32_t) * std::max<size_t>(p.task.size(), 1));
     if (e == hipSuccess) e = d_goff.reserve(sizeof(int64_t) * std::max<size_t>(p.goff.size(), 1));
-    if (e == hipSuccess) e = ctx->cm_tab.reserve(sizeof(uint32_t) * (size_t)std::max<int64_t>(p.tab_words, 1));
+    if (e == hipSuccess) e = ctx->set.cm_tab.reserve(sizeof(uint32_t) * (size_t)std::max<int64_t>(p.tab_words, 1));
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
     if (!p.task.empty()) GG_HIP_FN(hipMemcpyAsync(d_task.p, p.task.data(), sizeof(int32_t) * p.task.size(), hipMemcpyHostToDevice, ctx->stream));
     if (!p.goff.empty()) GG_HIP_FN(hipMemcpyAsync(d_goff.p, p.goff.data(), sizeof(int64_t) * p.goff.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -315,66 +291,47 @@ int upload_mode_plan(gg_ctx *ctx, const char *fn, const ModePlan &p, DevBuf &d_t
 }
 
 // The all-nodes plans are functions of the graph: built once behind the set adjacency, kept in the context and dropped by
-// gg_set_graph_csr (cm_valid, beside pn_valid).  The tasks of gg_partition_edges are (node, first entry) by the group widths of
-// the pair-neighbour sweep: d <= 8 -> 4 lanes, d <= 64 -> 16, else 64 with CM_CHUNK entries per task.
-int ensure_plans(gg_ctx *ctx, const char *fn, DevModePlan &dp) {
+// gg_set_graph_csr (SetGraph::drop): ctx->set.mode, and ctx->set.edges, the (node, first entry) tasks of gg_partition_edges by group
+// width (d <= 8 -> 4 lanes, d <= 64 -> 16, else 64) with CM_CHUNK entries per task and none for an empty list.
+int ensure_plans(gg_ctx *ctx, const char *fn) {
     const int rc = ensure_set_adjacency(ctx);
     if (rc != GG_OK) return rc;
-    if (!ctx->cm_valid) {
-        const int64_t *hp = ctx->h_pn_ptr.data();
-        const int n = ctx->n_node;
-        ModePlan p;
-        build_mode_plan(hp, nullptr, n, p);
-        DevModePlan tmp;
-        const int rc2 = upload_mode_plan(ctx, fn, p, ctx->cm_task, ctx->cm_goff, tmp);
-        if (rc2 != GG_OK) return rc2;
-        std::copy(p.first, p.first + CM_CLASSES + 1, ctx->cm_first);
-        ctx->cm_tab_words = p.tab_words;
-        std::vector<int2> et[3];
-        for (int v = 0; v < n; ++v) {
-            const int64_t d = hp[v + 1] - hp[v];
-            std::vector<int2> &dst = et[d <= 8 ? 0 : d <= 64 ? 1 : 2];
-            for (int64_t c0 = 0; c0 < d; c0 += CM_CHUNK) dst.push_back(make_int2(v, (int)c0));
-        }
-        const size_t total = et[0].size() + et[1].size() + et[2].size();
-        GG_CHECK(ctx, total <= 0x7fffffffull, GG_EINVAL, "%s: too many tasks", fn);
-        hipError_t e = ctx->cm_etask.reserve(sizeof(int2) * std::max<size_t>(total, 1));
-        if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
-        ctx->cm_efirst[0] = 0;
-        for (int c = 0; c < 3; ++c) {
-            if (!et[c].empty())
-                GG_HIP_FN(hipMemcpy(ctx->cm_etask.as<int2>() + ctx->cm_efirst[c], et[c].data(), sizeof(int2) * et[c].size(), hipMemcpyHostToDevice));
-            ctx->cm_efirst[c + 1] = ctx->cm_efirst[c] + (int64_t)et[c].size();
-        }
-        ctx->cm_valid = true;
-    }
-    dp.task = ctx->cm_task.as<int32_t>();
-    dp.goff = ctx->cm_goff.as<int64_t>();
-    std::copy(ctx->cm_first, ctx->cm_first + CM_CLASSES + 1, dp.first);
-    dp.tab_words = ctx->cm_tab_words;
+    SetGraph &g = ctx->set;
+    if (g.mode_valid) return GG_OK;
+    const int64_t *hp = g.h_ptr.data();
+    ModePlan p;
+    build_mode_plan(hp, nullptr, ctx->n_node, p);
+    const int rc2 = upload_mode_plan(ctx, fn, p, g.cm_task, g.cm_goff, g.mode);
+    if (rc2 != GG_OK) return rc2;
+    std::vector<int2> et;
+    GG_CHECK(ctx, plan_width_tasks(ctx->n_node, [&](int v) { return hp[v + 1] - hp[v]; }, {8, 64}, CM_CHUNK, false, et, g.edges.first), GG_EINVAL,
+             "%s: too many tasks", fn);
+    const hipError_t e = g.cm_etask.reserve(sizeof(int2) * std::max<size_t>(et.size(), 1));
+    if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
+    if (!et.empty()) GG_HIP_FN(hipMemcpy(g.cm_etask.p, et.data(), sizeof(int2) * et.size(), hipMemcpyHostToDevice));
+    g.edges.task = g.cm_etask.as<int2>();
+    g.mode_valid = true;
     return GG_OK;
 }
 
-// one sweep: the launches of the five classes (o.task / n_task / goff are set per class)
+// one sweep: the launches of the five classes (o.task / n_task are set per class)
 hipError_t launch_mode(gg_ctx *ctx, CmArgs o, const DevModePlan &dp) {
-    if (ctx->pn_max_deg > (1 << 30)) return hipErrorInvalidValue;  // (a table of 2 deg slots must stay below 2^32)
+    if (ctx->set.max_deg > (1 << 30)) return hipErrorInvalidValue;  // (a table of 2 deg slots must stay below 2^32)
     if (dp.tab_words) {
-        const hipError_t e = hipMemsetAsync(ctx->cm_tab.p, 0, sizeof(uint32_t) * (size_t)dp.tab_words, ctx->stream);
+        const hipError_t e = hipMemsetAsync(ctx->set.cm_tab.p, 0, sizeof(uint32_t) * (size_t)dp.tab_words, ctx->stream);
         if (e != hipSuccess) return e;
     }
-    o.tab = ctx->cm_tab.as<uint32_t>();
-    for (int c = 0; c < CM_CLASSES; ++c) {
+    o.tab = ctx->set.cm_tab.as<uint32_t>();
+    o.goff = dp.goff;
+    launch_width_classes(ctx->stream, CM_BLOCKS, dp.task, dp.first, o, cm_mode_group_kernel<4>, cm_mode_group_kernel<16>, cm_mode_group_kernel<64>);
+    for (int c = 3; c < CM_CLASSES; ++c) {  // the table kernels: one workgroup per task
         const int64_t n_task = dp.first[c + 1] - dp.first[c];
         if (n_task == 0) continue;
         o.task = dp.task + dp.first[c];
         o.n_task = (int)n_task;
-        o.goff = dp.goff;
-        const dim3 block(256);
-        if (c == 0) hipLaunchKernelGGL(cm_mode_group_kernel<4>, dim3(std::min(CM_BLOCKS, cdiv(n_task, 64))), block, 0, ctx->stream, o);
-        else if (c == 1) hipLaunchKernelGGL(cm_mode_group_kernel<16>, dim3(std::min(CM_BLOCKS, cdiv(n_task, 16))), block, 0, ctx->stream, o);
-        else if (c == 2) hipLaunchKernelGGL(cm_mode_group_kernel<64>, dim3(std::min(CM_BLOCKS, cdiv(n_task, 4))), block, 0, ctx->stream, o);
-        else if (c == 3) hipLaunchKernelGGL(cm_mode_table_kernel<false>, dim3((unsigned)std::min<int64_t>(CM_BLOCKS, n_task)), block, 0, ctx->stream, o);
-        else hipLaunchKernelGGL(cm_mode_table_kernel<true>, dim3((unsigned)std::min<int64_t>(CM_BLOCKS, n_task)), block, 0, ctx->stream, o);
+        const dim3 grid((unsigned)std::min<int64_t>(CM_BLOCKS, n_task)), block(256);
+        if (c == 3) hipLaunchKernelGGL(cm_mode_table_kernel<false>, grid, block, 0, ctx->stream, o);
+        else hipLaunchKernelGGL(cm_mode_table_kernel<true>, grid, block, 0, ctx->stream, o);
     }
     return hipGetLastError();
 }
@@ -399,23 +356,25 @@ extern "C" int gg_neighbor_mode(gg_ctx *ctx, const int32_t *labels, uint32_t sal
     GG_CHECK(ctx, labels && out, GG_EINVAL, "%s: labels and out must not be NULL", fn);
     GG_CHECK(ctx, m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld does not fit in 31 bits", fn, (long long)m);
     for (int v = 0; v < n; ++v) GG_CHECK(ctx, labels[v] >= 0, GG_EINVAL, "%s: labels[%d] = %d is negative", fn, v, labels[v]);
-    if (nodes)
-        for (int64_t i = 0; i < m; ++i)
-            GG_CHECK(ctx, nodes[i] >= 0 && nodes[i] < n, GG_EINVAL, "%s: nodes[%lld] = %d out of range [0, %d)", fn, (long long)i, nodes[i], n);
+    if (nodes) {
+        const int rc = check_ids(ctx, fn, "nodes", nodes, m);
+        if (rc != GG_OK) return rc;
+    }
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    DevModePlan dp;
+    DevModePlan own;  // the plan of a request of some nodes
     ScopedBuf d_task, d_goff;
     if (nodes) {
         const int rc = ensure_set_adjacency(ctx);
         if (rc != GG_OK) return rc;
         ModePlan p;
-        build_mode_plan(ctx->h_pn_ptr.data(), nodes, m, p);
-        const int rc2 = upload_mode_plan(ctx, fn, p, d_task, d_goff, dp);
+        build_mode_plan(ctx->set.h_ptr.data(), nodes, m, p);
+        const int rc2 = upload_mode_plan(ctx, fn, p, d_task, d_goff, own);
         if (rc2 != GG_OK) return rc2;
     } else {
-        const int rc = ensure_plans(ctx, fn, dp);
+        const int rc = ensure_plans(ctx, fn);
         if (rc != GG_OK) return rc;
     }
+    const DevModePlan &dp = nodes ? own : ctx->set.mode;
     ScopedBuf d_lab, d_out, d_nodes;
     hipError_t e = d_lab.reserve(sizeof(int32_t) * (size_t)n);
     if (e == hipSuccess) e = d_out.reserve(sizeof(int32_t) * (size_t)m);
@@ -425,8 +384,8 @@ extern "C" int gg_neighbor_mode(gg_ctx *ctx, const int32_t *labels, uint32_t sal
     if (nodes) GG_HIP_FN(hipMemcpyAsync(d_nodes.p, nodes, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     CmArgs o{};
     o.nodes = nodes ? d_nodes.as<int32_t>() : nullptr;
-    o.ptr = ctx->pn_ptr.as<int64_t>();
-    o.adj = ctx->pn_adj.as<int32_t>();
+    o.ptr = ctx->set.ptr.as<int64_t>();
+    o.adj = ctx->set.adj.as<int32_t>();
     o.labels = d_lab.as<int32_t>();
     o.out = d_out.as<int32_t>();
     o.salt = salt;
@@ -453,9 +412,9 @@ extern "C" int gg_label_propagation(gg_ctx *ctx, uint32_t seed, int32_t max_iter
     GG_CHECK(ctx, labels && iters && converged && changed, GG_EINVAL, "%s: labels, iters, converged and changed must not be NULL", fn);
     const int n = ctx->n_node;
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    DevModePlan dp;
-    const int rc = ensure_plans(ctx, fn, dp);
+    const int rc = ensure_plans(ctx, fn);
     if (rc != GG_OK) return rc;
+    const DevModePlan &dp = ctx->set.mode;
     // the state lives on the device for the whole call: L before and behind a half-step (ping-pong) and one changed word per iteration
     ScopedBuf d_L[2], d_changed;
     hipError_t e = d_L[0].reserve(sizeof(int32_t) * (size_t)std::max(n, 1));
@@ -464,8 +423,8 @@ extern "C" int gg_label_propagation(gg_ctx *ctx, uint32_t seed, int32_t max_iter
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
     GG_HIP_FN(hipMemsetAsync(d_changed.p, 0, sizeof(unsigned int) * (size_t)max_iters, ctx->stream));
     CmArgs o{};
-    o.ptr = ctx->pn_ptr.as<int64_t>();
-    o.adj = ctx->pn_adj.as<int32_t>();
+    o.ptr = ctx->set.ptr.as<int64_t>();
+    o.adj = ctx->set.adj.as<int32_t>();
     o.keep = 1;
     (void)hipEventRecord(ctx->ev0, ctx->stream);
     if (n) hipLaunchKernelGGL(cm_iota_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_L[0].as<int32_t>(), n);
@@ -509,8 +468,7 @@ extern "C" int gg_partition_edges(gg_ctx *ctx, const int32_t *assign, int32_t n_
     for (int v = 0; v < n; ++v)
         GG_CHECK(ctx, assign[v] >= -1 && assign[v] < n_label, GG_EINVAL, "%s: assign[%d] = %d outside [-1, %d)", fn, v, assign[v], n_label);
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    DevModePlan dp;
-    const int rc = ensure_plans(ctx, fn, dp);
+    const int rc = ensure_plans(ctx, fn);
     if (rc != GG_OK) return rc;
     ScopedBuf d_assign, d_cnt;
     hipError_t e = d_assign.reserve(sizeof(int32_t) * (size_t)std::max(n, 1));
@@ -519,22 +477,13 @@ extern "C" int gg_partition_edges(gg_ctx *ctx, const int32_t *assign, int32_t n_
     if (n) GG_HIP_FN(hipMemcpyAsync(d_assign.p, assign, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     GG_HIP_FN(hipMemsetAsync(d_cnt.p, 0, sizeof(int64_t) * 2 * (size_t)n_label, ctx->stream));
     CeArgs o{};
-    o.ptr = ctx->pn_ptr.as<int64_t>();
-    o.adj = ctx->pn_adj.as<int32_t>();
+    o.ptr = ctx->set.ptr.as<int64_t>();
+    o.adj = ctx->set.adj.as<int32_t>();
     o.assign = d_assign.as<int32_t>();
     o.intra = d_cnt.as<unsigned long long>();
     o.tot = o.intra + n_label;
     (void)hipEventRecord(ctx->ev0, ctx->stream);
-    for (int c = 0; c < 3; ++c) {
-        o.task = ctx->cm_etask.as<int2>() + ctx->cm_efirst[c];
-        o.n_task = (int)(ctx->cm_efirst[c + 1] - ctx->cm_efirst[c]);
-        if (o.n_task == 0) continue;
-        const int W = c == 0 ? 4 : c == 1 ? 16 : 64;
-        const dim3 grid(std::min(CM_BLOCKS, cdiv(o.n_task, 256 / W)));
-        if (c == 0) hipLaunchKernelGGL(cm_edges_kernel<4>, grid, dim3(256), 0, ctx->stream, o);
-        else if (c == 1) hipLaunchKernelGGL(cm_edges_kernel<16>, grid, dim3(256), 0, ctx->stream, o);
-        else hipLaunchKernelGGL(cm_edges_kernel<64>, grid, dim3(256), 0, ctx->stream, o);
-    }
+    launch_width_classes(ctx->stream, CM_BLOCKS, ctx->set.edges.task, ctx->set.edges.first, o, cm_edges_kernel<4>, cm_edges_kernel<16>, cm_edges_kernel<64>);
     (void)hipEventRecord(ctx->ev1, ctx->stream);
     GG_HIP_FN(hipGetLastError());
     GG_HIP_FN(hipMemcpyAsync(intra, d_cnt.p, sizeof(int64_t) * (size_t)n_label, hipMemcpyDeviceToHost, ctx->stream));

@@ -529,9 +529,10 @@ int gg_destroy(gg_ctx *ctx) {
                       &ctx->step_u, &ctx->step_v, &ctx->step_x, &ctx->sg_rows, &ctx->sg_bias, &ctx->touched_ptr, &ctx->x_cnt, &ctx->x_send_ids, &ctx->x_send_rows,
                       &ctx->x_recv_ids, &ctx->x_recv_rows, &ctx->x_nglob, &ctx->x_own, &ctx->st_item, &ctx->st_item2, &ctx->st_cur, &ctx->st_prev, &ctx->st_len,
                       &ctx->st_alive, &ctx->st_rank, &ctx->bfs_key, &ctx->bfs_bm, &ctx->bfs_misc, &ctx->bfs_sparse, &ctx->bfs_rowptr32, &ctx->lv_pfx, &ctx->dc_keys, &ctx->dc_vals, &ctx->dc_words, &ctx->lv_beg, &ctx->lv_k, &ctx->lv_chunks, &ctx->lv_coff, &ctx->lv_scores, &ctx->lv_chunk_owner, &ctx->lv_prefix, &ctx->lv_big, &ctx->lv_fe, &ctx->fin_list, &ctx->table_bad, &ctx->hub_acc,
-                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj, &ctx->pn_ptr, &ctx->pn_adj, &ctx->gp_task, &ctx->gp_hub, &ctx->gp_stage, &ctx->cm_task, &ctx->cm_goff, &ctx->cm_tab, &ctx->cm_etask, &ctx->th_tab,
+                      &ctx->q3_store, &ctx->q3s_off, &ctx->ep_center, &ctx->ep_neighbor, &ctx->ep_label, &ctx->ep_node1, &ctx->ep_node2, &ctx->ep_reward, &ctx->topk_adj,
                       &ctx->gs_es, &ctx->gs_cpre, &ctx->pt_starts, &ctx->pt_paths, &ctx->pt_len, &ctx->pt_cnt, &ctx->pt_ptr, &ctx->pt_noise, &ctx->pt_sample};
     for (DevBuf *b : bufs) b->release();
+    ctx->set.release();
     for (StageIndex *ix : {&ctx->sg_own, &ctx->sg_early}) ix->release();
     for (hipEvent_t e : ctx->lv_ev)
         if (e) (void)hipEventDestroy(e);
@@ -581,11 +582,7 @@ int gg_set_graph_csr(gg_ctx *ctx, const int64_t *rowptr, const int32_t *col) {
     ctx->bfs_rowptr32_valid = false;
     ctx->topk_adj.release();  // (the sorted copy of gg_topk_scores is rebuilt from the new lists on first use)
     ctx->topk_adj_valid = false;
-    ctx->pn_ptr.release();  // (the set adjacency of gg_pair_neighbors likewise)
-    ctx->pn_adj.release();
-    ctx->pn_valid = false;
-    ctx->gp_valid = false;  // (the task plan of the neighbour-sum sweep is laid out by the set adjacency's degrees: graph_prop.hip)
-    ctx->cm_valid = false;  // (so are the task plans of the neighbour-mode sweep and of gg_partition_edges: communities.hip)
+    ctx->set.drop();  // (the set adjacency of gg_pair_neighbors likewise, with the task plans laid out by its degrees: set_sweep.h)
     ctx->gs_es_valid = ctx->gs_cpre_valid = false;  // (gg_graph_softmax's edge scores are indexed by the edges of the graph)
     ctx->pt_noise_set = false;  // (the pre-training noise weights were chosen for the old graph's degrees)
     GG_HIP(ctx, hipMalloc((void **)&ctx->g_rowptr, sizeof(int64_t) * (n + 1)));

@@ -67,6 +67,53 @@ struct Model {
     float lr = 1e-3f, lambda = 1e-5f;
 };
 
+// The state of the graph-only sweeps over the SET adjacency of the resident graph (pair_neighbors.hip, graph_prop.hip, communities.hip,
+// two_hop.hip; shared parts: set_sweep.h).  The plans name device buffers: a call's own (a request of some nodes) or the context's.
+struct DevSumPlan {   // graph_prop.hip: tasks (row, first entry, stage row or -1) and hubs (row, first stage row, chunks)
+    const int4 *task = nullptr, *hub = nullptr;
+    int n_task = 0, n_hub = 0;
+    int64_t n_stage = 0;
+};
+struct DevModePlan {  // communities.hip: request rows ordered by class (4, 16, 64 lanes, the LDS table, the global table)
+    const int32_t *task = nullptr;
+    const int64_t *goff = nullptr;  // the first table word of each global-table task
+    int64_t first[6] = {};
+    int64_t tab_words = 0;
+};
+struct DevWidthTasks {  // set_sweep.h: (item, first entry) tasks ordered by group width (4, 16, 64 lanes)
+    const int2 *task = nullptr;
+    int64_t first[4] = {};
+};
+struct SetGraph {
+    // every node's list sorted, distinct and without the node itself, under row offsets of its own, with host copies (the degrees
+    // and the plans come from them); built by ensure_set_adjacency on first use
+    DevBuf ptr, adj;
+    std::vector<int64_t> h_ptr;
+    std::vector<int32_t> h_adj;
+    int32_t max_deg = 0;
+    bool valid = false;
+    // the all-nodes plans are functions of the graph alone: built on first use behind the adjacency (ensure_sweep_plan, ensure_plans)
+    DevBuf gp_task, gp_hub;
+    DevSumPlan sum;
+    bool sum_valid = false;
+    DevBuf cm_task, cm_goff, cm_etask;
+    DevModePlan mode;
+    DevWidthTasks edges;  // gg_partition_edges
+    bool mode_valid = false;
+    // scratch of the call in flight: the hubs' partial rows (graph_prop.hip), the global tables (communities.hip, two_hop.hip)
+    DevBuf gp_stage, cm_tab, th_tab;
+    // a new graph (gg_set_graph_csr): the adjacency and every plan go, the plan and scratch buffers keep their capacity
+    void drop() {
+        ptr.release();
+        adj.release();
+        valid = sum_valid = mode_valid = false;
+    }
+    void release() {
+        drop();
+        for (DevBuf *b : {&gp_task, &gp_hub, &cm_task, &cm_goff, &cm_etask, &gp_stage, &cm_tab, &th_tab}) b->release();
+    }
+};
+
 }  // namespace gg
 
 struct gg_ctx {
@@ -309,36 +356,8 @@ struct gg_ctx {
     gg::DevBuf topk_adj;
     bool topk_adj_valid = false;
 
-    // gg_pair_neighbors / gg_distinct_degrees (pair_neighbors.hip): the SET adjacency of the resident graph -- every list sorted,
-    // distinct and without the node itself, under row offsets of its own (host copy: h_pn_ptr) -- built by ensure_set_adjacency on
-    // first use; dropped by gg_set_graph_csr
-    gg::DevBuf pn_ptr, pn_adj;
-    std::vector<int64_t> h_pn_ptr;
-    std::vector<int32_t> h_pn_adj;  // host copy of the lists (the two-hop sweep plans from it)
-    int32_t pn_max_deg = 0;
-    bool pn_valid = false;
-
-    // gg_neighbor_sum / gg_label_spread (graph_prop.hip): the task plan of the all-nodes neighbour-sum sweep over that set adjacency --
-    // tasks (row, first entry, stage row or -1) and hubs (row, first stage row, chunks) -- a function of the graph alone: built on
-    // first use, dropped by gg_set_graph_csr beside pn_valid; gp_stage holds the hubs' partial rows of the call in flight
-    gg::DevBuf gp_task, gp_hub, gp_stage;
-    int32_t gp_n_task = 0, gp_n_hub = 0;
-    int64_t gp_n_stage = 0;
-    bool gp_valid = false;
-
-    // gg_neighbor_mode / gg_label_propagation / gg_partition_edges (communities.hip): the all-nodes task plans over the set adjacency --
-    // the neighbour-mode tasks (request rows ordered by class: 4, 16, 64 lanes, the LDS table, the global table; cm_goff: the first
-    // table word of each global-table task) and the (node, first entry) tasks of gg_partition_edges by group width -- functions of
-    // the graph alone: built on first use, dropped by gg_set_graph_csr beside pn_valid; cm_tab holds the global tables of the call
-    // in flight
-    gg::DevBuf cm_task, cm_goff, cm_tab, cm_etask;
-    int64_t cm_first[6] = {}, cm_efirst[4] = {};
-    int64_t cm_tab_words = 0;
-    bool cm_valid = false;
-
-    // gg_two_hop_topk / gg_two_hop_rank (two_hop.hip): the zeroed (column, uint64 sum) tables of the global-table queries of the pass in
-    // flight; the task plan is per call, so gg_set_graph_csr drops nothing
-    gg::DevBuf th_tab;
+    // the SET adjacency of the resident graph, the all-nodes task plans of the sweeps over it and their scratch (gg::SetGraph above)
+    gg::SetGraph set;
 
     // gg_graph_softmax (graph_softmax.hip): a PRIVATE copy of the generator's edge scores (the walk sampler's cache and stamps are
     // never touched), valid until generator_changed; the per-node offsets of its 16-edge fill chunks, valid until gg_set_graph_csr
@@ -390,7 +409,7 @@ int fail(gg_ctx *ctx, int code, const char *fmt, ...);
 // exclusive scan of n int32 counts into n+1 int64 offsets (prepare.hip)
 int device_exclusive_scan(gg_ctx *ctx, const int32_t *cnt, int64_t *ptr, int64_t n);
 int ensure_sorted_adjacency(gg_ctx *ctx);  // topk_score.hip: ctx->topk_adj (every node's list sorted), built on first use
-int ensure_set_adjacency(gg_ctx *ctx);  // pair_neighbors.hip: ctx->pn_ptr / pn_adj (sorted distinct lists without the node itself), built on first use
+int ensure_set_adjacency(gg_ctx *ctx);  // pair_neighbors.hip: ctx->set (sorted distinct lists without the node itself), built on first use
 int ensure_g_pairs(gg_ctx *ctx);  // prepare.hip: (node_1, node_2) of the resident G walks, written on first use
 int device_compact_flags(gg_ctx *ctx, const int32_t *flag, int64_t n, int32_t *list, int64_t *total_out);  // prepare.hip
 int device_segment_rows(gg_ctx *ctx, const int32_t *cnt, int64_t n, int T, int32_t *off, int4 *list, int64_t *totals, hipStream_t stream = nullptr,

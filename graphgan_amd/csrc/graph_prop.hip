@@ -19,7 +19,7 @@
 // variant (EPI) of the ONE sweep kernel, so a fit of T iterations equals T primitive calls composed on the host, bit for bit.
 #include <algorithm>
 
-#include "gg_internal.h"
+#include "set_sweep.h"
 
 namespace gg {
 
@@ -194,6 +194,7 @@ __global__ __launch_bounds__(256) void gp_rows_kernel(const float *F, const int3
 }
 
 // The tasks of a request: the chunk tasks of the hubs first (the longest work starts first), then one task per other node.
+// (Not set_sweep.h's planner: one width, hubs ahead of the rest, and every chunk task carries its stage row.)
 struct Plan {
     std::vector<int4> task, hub;
     int64_t n_stage = 0;
@@ -220,14 +221,7 @@ bool build_plan(const int64_t *hp, const int32_t *nodes, int64_t m, Plan &p) {
     return true;
 }
 
-// a request's plan on the device: the context's (all nodes) or a call's own
-struct DevPlan {
-    const int4 *task = nullptr, *hub = nullptr;
-    int n_task = 0, n_hub = 0;
-    int64_t n_stage = 0;
-};
-
-int upload_plan(gg_ctx *ctx, const char *fn, const Plan &p, DevBuf &d_task, DevBuf &d_hub, DevPlan &dp) {
+int upload_plan(gg_ctx *ctx, const char *fn, const Plan &p, DevBuf &d_task, DevBuf &d_hub, DevSumPlan &dp) {
     hipError_t e = d_task.reserve(sizeof(int4) * std::max<size_t>(p.task.size(), 1));
     if (e == hipSuccess) e = d_hub.reserve(sizeof(int4) * std::max<size_t>(p.hub.size(), 1));
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
@@ -243,31 +237,22 @@ int upload_plan(gg_ctx *ctx, const char *fn, const Plan &p, DevBuf &d_task, DevB
 }
 
 // The plan of the all-nodes sweep is a function of the graph: built once behind the set adjacency, kept in the context and
-// dropped by gg_set_graph_csr (gp_valid, beside pn_valid).
-int ensure_sweep_plan(gg_ctx *ctx, const char *fn, DevPlan &dp) {
+// dropped by gg_set_graph_csr (SetGraph::drop): ctx->set.sum.
+int ensure_sweep_plan(gg_ctx *ctx, const char *fn) {
     const int rc = ensure_set_adjacency(ctx);
     if (rc != GG_OK) return rc;
-    if (!ctx->gp_valid) {
-        Plan p;
-        GG_CHECK(ctx, build_plan(ctx->h_pn_ptr.data(), nullptr, ctx->n_node, p), GG_EINVAL, "%s: too many tasks", fn);
-        DevPlan tmp;
-        const int rc2 = upload_plan(ctx, fn, p, ctx->gp_task, ctx->gp_hub, tmp);
-        if (rc2 != GG_OK) return rc2;
-        ctx->gp_n_task = tmp.n_task;
-        ctx->gp_n_hub = tmp.n_hub;
-        ctx->gp_n_stage = tmp.n_stage;
-        ctx->gp_valid = true;
-    }
-    dp.task = ctx->gp_task.as<int4>();
-    dp.hub = ctx->gp_hub.as<int4>();
-    dp.n_task = ctx->gp_n_task;
-    dp.n_hub = ctx->gp_n_hub;
-    dp.n_stage = ctx->gp_n_stage;
+    SetGraph &g = ctx->set;
+    if (g.sum_valid) return GG_OK;
+    Plan p;
+    GG_CHECK(ctx, build_plan(g.h_ptr.data(), nullptr, ctx->n_node, p), GG_EINVAL, "%s: too many tasks", fn);
+    const int rc2 = upload_plan(ctx, fn, p, g.gp_task, g.gp_hub, g.sum);
+    if (rc2 != GG_OK) return rc2;
+    g.sum_valid = true;
     return GG_OK;
 }
 
 template <int EPI>
-void launch_sweep(hipStream_t stream, int lpr, const GpArgs &o, const DevPlan &dp) {
+void launch_sweep(hipStream_t stream, int lpr, const GpArgs &o, const DevSumPlan &dp) {
     if (o.n_task) {
         const dim3 grid(std::min(GP_BLOCKS, cdiv(o.n_task, 4))), block(256);
         switch (lpr) {
@@ -287,13 +272,6 @@ int lanes_per_row(int CP) {
     int lpr = 1;
     while (lpr < CP / 4) lpr <<= 1;
     return lpr;
-}
-
-// first id outside [0, n_node), or -1
-int64_t first_bad_id(const int32_t *ids, int64_t m, int n_node) {
-    for (int64_t i = 0; i < m; ++i)
-        if (ids[i] < 0 || ids[i] >= n_node) return i;
-    return -1;
 }
 
 // host rows [rows, n_col] <-> device rows [rows, CP], on the stream
@@ -324,23 +302,24 @@ extern "C" int gg_neighbor_sum(gg_ctx *ctx, const float *X, int32_t n_col, const
     GG_CHECK(ctx, X && out, GG_EINVAL, "%s: X and out must not be NULL", fn);
     GG_CHECK(ctx, m <= 0x7fffffffLL, GG_EINVAL, "%s: m = %lld does not fit in 31 bits", fn, (long long)m);
     if (nodes) {
-        const int64_t bad = first_bad_id(nodes, m, n);
-        GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: nodes[%lld] = %d out of range [0, %d)", fn, (long long)bad, nodes[bad], n);
+        const int rc = check_ids(ctx, fn, "nodes", nodes, m);
+        if (rc != GG_OK) return rc;
     }
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    DevPlan dp;
+    DevSumPlan own;  // the plan of a request of some nodes
     ScopedBuf d_task, d_hub;
     if (nodes) {
         const int rc = ensure_set_adjacency(ctx);
         if (rc != GG_OK) return rc;
         Plan p;
-        GG_CHECK(ctx, build_plan(ctx->h_pn_ptr.data(), nodes, m, p), GG_EINVAL, "%s: too many tasks", fn);
-        const int rc2 = upload_plan(ctx, fn, p, d_task, d_hub, dp);
+        GG_CHECK(ctx, build_plan(ctx->set.h_ptr.data(), nodes, m, p), GG_EINVAL, "%s: too many tasks", fn);
+        const int rc2 = upload_plan(ctx, fn, p, d_task, d_hub, own);
         if (rc2 != GG_OK) return rc2;
     } else {
-        const int rc = ensure_sweep_plan(ctx, fn, dp);
+        const int rc = ensure_sweep_plan(ctx, fn);
         if (rc != GG_OK) return rc;
     }
+    const DevSumPlan &dp = nodes ? own : ctx->set.sum;
     const int CP = 4 * cdiv(n_col, 4);
     const size_t row = sizeof(float) * CP;
     ScopedBuf d_X, d_out, d_in, d_os, d_nodes;
@@ -349,7 +328,7 @@ extern "C" int gg_neighbor_sum(gg_ctx *ctx, const float *X, int32_t n_col, const
     if (e == hipSuccess && in_scale) e = d_in.reserve(sizeof(float) * n);
     if (e == hipSuccess && out_scale) e = d_os.reserve(sizeof(float) * n);
     if (e == hipSuccess && nodes) e = d_nodes.reserve(sizeof(int32_t) * (size_t)m);
-    if (e == hipSuccess) e = ctx->gp_stage.reserve(row * std::max<int64_t>(dp.n_stage, 1));
+    if (e == hipSuccess) e = ctx->set.gp_stage.reserve(row * std::max<int64_t>(dp.n_stage, 1));
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
     if (CP != n_col) GG_HIP_FN(hipMemsetAsync(d_X.p, 0, row * n, ctx->stream));  // (the padding columns are exact zeros)
     GG_HIP_FN(copy_rows(d_X.p, row, X, sizeof(float) * n_col, n_col, n, hipMemcpyHostToDevice, ctx->stream));
@@ -360,11 +339,11 @@ extern "C" int gg_neighbor_sum(gg_ctx *ctx, const float *X, int32_t n_col, const
     o.task = dp.task;
     o.n_task = dp.n_task;
     o.nodes = nodes ? d_nodes.as<int32_t>() : nullptr;
-    o.ptr = ctx->pn_ptr.as<int64_t>();
-    o.adj = ctx->pn_adj.as<int32_t>();
+    o.ptr = ctx->set.ptr.as<int64_t>();
+    o.adj = ctx->set.adj.as<int32_t>();
     o.X = d_X.as<float>();
     o.in_scale = in_scale ? d_in.as<float>() : nullptr;
-    o.stage = ctx->gp_stage.as<float>();
+    o.stage = ctx->set.gp_stage.as<float>();
     o.e.out = d_out.as<float>();
     o.e.n_col = n_col;
     o.e.CP = CP;
@@ -399,8 +378,8 @@ extern "C" int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes, const ui
     GG_CHECK(ctx, m_out == 0 || F_out, GG_EINVAL, "%s: F_out must not be NULL", fn);
     GG_CHECK(ctx, alpha > 0.0 && alpha < 1.0, GG_EINVAL, "%s: alpha = %g outside (0, 1)", fn, alpha);
     GG_CHECK(ctx, iters >= 1, GG_EINVAL, "%s: iters = %d is below 1", fn, iters);
-    int64_t bad = first_bad_id(train_nodes, m_train, n);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: train_nodes[%lld] = %d out of range [0, %d)", fn, (long long)bad, train_nodes[bad], n);
+    int rc = check_ids(ctx, fn, "train_nodes", train_nodes, m_train);
+    if (rc != GG_OK) return rc;
     {
         std::vector<int64_t> seen((size_t)n, -1);
         for (int64_t j = 0; j < m_train; ++j) {
@@ -415,13 +394,13 @@ extern "C" int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes, const ui
             GG_CHECK(ctx, (label_bits[j * CW + CW - 1] >> (n_class % 32)) == 0, GG_EINVAL, "%s: label_bits row %lld has a bit set at a position >= n_class = %d", fn,
                      (long long)j, n_class);
     if (out_nodes) {
-        bad = first_bad_id(out_nodes, m_out, n);
-        GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: out_nodes[%lld] = %d out of range [0, %d)", fn, (long long)bad, out_nodes[bad], n);
+        rc = check_ids(ctx, fn, "out_nodes", out_nodes, m_out);
+        if (rc != GG_OK) return rc;
     }
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    DevPlan dp;
-    const int rc = ensure_sweep_plan(ctx, fn, dp);
+    rc = ensure_sweep_plan(ctx, fn);
     if (rc != GG_OK) return rc;
+    const DevSumPlan &dp = ctx->set.sum;
     const int CP = 4 * cdiv(n_class, 4);
     const size_t row = sizeof(float) * CP;
     // the state lives on the device for the whole call: F_t and F_{t+1} (ping-pong), the label masks of every node (Y0 as bits)
@@ -436,7 +415,7 @@ extern "C" int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes, const ui
     if (e == hipSuccess) e = d_delta.reserve(sizeof(unsigned int));
     if (e == hipSuccess && out_nodes && m_out) e = d_onodes.reserve(sizeof(int32_t) * (size_t)m_out);
     if (e == hipSuccess && out_nodes && m_out) e = d_orows.reserve(row * (size_t)m_out);
-    if (e == hipSuccess) e = ctx->gp_stage.reserve(row * std::max<int64_t>(dp.n_stage, 1));
+    if (e == hipSuccess) e = ctx->set.gp_stage.reserve(row * std::max<int64_t>(dp.n_stage, 1));
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
     GG_HIP_FN(hipMemcpyAsync(d_s.p, s, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
     GG_HIP_FN(hipMemcpyAsync(d_a.p, a, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -454,10 +433,10 @@ extern "C" int gg_label_spread(gg_ctx *ctx, const int32_t *train_nodes, const ui
     GpArgs o{};
     o.task = dp.task;
     o.n_task = dp.n_task;
-    o.ptr = ctx->pn_ptr.as<int64_t>();
-    o.adj = ctx->pn_adj.as<int32_t>();
+    o.ptr = ctx->set.ptr.as<int64_t>();
+    o.adj = ctx->set.adj.as<int32_t>();
     o.in_scale = d_s.as<float>();
-    o.stage = ctx->gp_stage.as<float>();
+    o.stage = ctx->set.gp_stage.as<float>();
     o.e.n_col = n_class;
     o.e.CP = CP;
     o.e.a = d_a.as<float>();

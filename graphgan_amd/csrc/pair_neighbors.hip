@@ -11,7 +11,7 @@
 //   a group     W adjacent lanes take a task: lane l walks the entries c0 + l, c0 + l + W, ... and looks each one up in the
 //               longer list.  A lane's entries ascend, so each search starts where the lane's previous one ended;
 //   W           from the shorter list's length s: s <= 8 -> 4, s <= 64 -> 16, else 64 (a whole wavefront per pair would idle
-//               on a graph of mean degree 5);
+//               on a graph of mean degree 5) -- the planner and the launcher of set_sweep.h;
 //   a long pair s > PN_CHUNK: ceil(s / PN_CHUNK) tasks at W = 64 -- one wavefront never walks a hub's whole list -- which ADD
 //               their partial results into the zeroed outputs with integer atomics.  Every other pair has one task, which
 //               stores.
@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <thread>
 
-#include "gg_internal.h"
+#include "set_sweep.h"
 
 namespace gg {
 
@@ -62,12 +62,7 @@ __global__ __launch_bounds__(256) void pn_sweep_kernel(PnArgs o) {
         unsigned long long ws[PN_MAX_W] = {0ull, 0ull, 0ull, 0ull};
         for (int e = c0 + gl; e < end; e += W) {
             const int x = A[e];
-            int hi = blen;  // first position of B at or behind x, from the lane's previous position on
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (B[mid] < x) lo = mid + 1;
-                else hi = mid;
-            }
+            lo = set_lower_bound(B, lo, blen, x);  // from the lane's previous position on
             if (lo < blen && B[lo] == x && x != u && x != v) {
                 ++cnt;
 #pragma unroll
@@ -103,25 +98,17 @@ __global__ __launch_bounds__(256) void pn_sweep_kernel(PnArgs o) {
     }
 }
 
-// first id outside [0, n_node), or -1
-int64_t bad_id(const int32_t *ids, int64_t m, int n_node) {
-    for (int64_t i = 0; i < m; ++i)
-        if (ids[i] < 0 || ids[i] >= n_node) return i;
-    return -1;
-}
-
-int width_class(int s) { return s <= 8 ? 0 : s <= 64 ? 1 : 2; }
-
 }  // namespace
 
 // The set adjacency of the resident graph: per node the sorted distinct neighbours other than the node itself, under int64 row
-// offsets of its own (host copy: h_pn_ptr).  Built on first use after gg_set_graph_csr, which drops it; the resident lists and
+// offsets of its own (ctx->set, with host copies).  Built on first use after gg_set_graph_csr, which drops it; the resident lists and
 // the sorted copy of ensure_sorted_adjacency (which keeps duplicates and self-loops) are not touched.
 int ensure_set_adjacency(gg_ctx *ctx) {
-    if (ctx->pn_valid) return GG_OK;
+    SetGraph &g = ctx->set;
+    if (g.valid) return GG_OK;
     const int n = ctx->n_node;
     std::vector<int32_t> s(ctx->h_col);
-    std::vector<int64_t> &ptr = ctx->h_pn_ptr;
+    std::vector<int64_t> &ptr = g.h_ptr;
     ptr.assign((size_t)n + 1, 0);
     const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::vector<std::thread> th;
@@ -143,15 +130,15 @@ int ensure_set_adjacency(gg_ctx *ctx) {
         ptr[v + 1] = ptr[v] + len;
     }
     const size_t total = (size_t)ptr[n];
-    hipError_t e = ctx->pn_ptr.reserve(sizeof(int64_t) * ((size_t)n + 1));
-    if (e == hipSuccess) e = ctx->pn_adj.reserve(sizeof(int32_t) * std::max<size_t>(total, 1));
-    if (e == hipSuccess) e = hipMemcpy(ctx->pn_ptr.p, ptr.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess && total) e = hipMemcpy(ctx->pn_adj.p, s.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice);
+    hipError_t e = g.ptr.reserve(sizeof(int64_t) * ((size_t)n + 1));
+    if (e == hipSuccess) e = g.adj.reserve(sizeof(int32_t) * std::max<size_t>(total, 1));
+    if (e == hipSuccess) e = hipMemcpy(g.ptr.p, ptr.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess && total) e = hipMemcpy(g.adj.p, s.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "set adjacency (%lld entries): %s", (long long)total, hipGetErrorString(e));
     s.resize(total);
-    ctx->h_pn_adj.swap(s);  // (the host copy of the lists: the two-hop sweep plans its queries from it, two_hop.hip)
-    ctx->pn_max_deg = (int32_t)max_deg;
-    ctx->pn_valid = true;
+    g.h_adj.swap(s);  // (the host copy of the lists: the two-hop sweep plans its queries from it, two_hop.hip)
+    g.max_deg = (int32_t)max_deg;
+    g.valid = true;
     return GG_OK;
 }
 
@@ -167,7 +154,7 @@ extern "C" int gg_distinct_degrees(gg_ctx *ctx, int32_t *deg) {
     GG_HIP(ctx, hipSetDevice(ctx->device));
     const int rc = ensure_set_adjacency(ctx);
     if (rc != GG_OK) return rc;
-    for (int v = 0; v < ctx->n_node; ++v) deg[v] = (int32_t)(ctx->h_pn_ptr[v + 1] - ctx->h_pn_ptr[v]);
+    for (int v = 0; v < ctx->n_node; ++v) deg[v] = (int32_t)(ctx->set.h_ptr[v + 1] - ctx->set.h_ptr[v]);
     return GG_OK;
 }
 
@@ -184,20 +171,15 @@ extern "C" int gg_pair_neighbors(gg_ctx *ctx, const int32_t *u, const int32_t *v
     GG_CHECK(ctx, u && v, GG_EINVAL, "%s: u and v must not be NULL", fn);
     GG_CHECK(ctx, cn && deg_u && deg_v, GG_EINVAL, "%s: cn, deg_u and deg_v must not be NULL", fn);
     const int n = ctx->n_node;
-    int64_t bad = bad_id(u, m, n);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: u[%lld] = %d out of range [0, %d)", fn, (long long)bad, u[bad], n);
-    bad = bad_id(v, m, n);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: v[%lld] = %d out of range [0, %d)", fn, (long long)bad, v[bad], n);
-    GG_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = ensure_set_adjacency(ctx);
+    int rc = check_ids(ctx, fn, "u", u, m);
+    if (rc == GG_OK) rc = check_ids(ctx, fn, "v", v, m);
     if (rc != GG_OK) return rc;
-    // a sum has at most max(deg) terms: it must stay below 2^63
-    uint64_t max_w = 0;
-    for (int64_t k = 0; k < (int64_t)n_w * n; ++k) max_w = std::max(max_w, weights[k]);
-    GG_CHECK(ctx, max_w == 0 || ctx->pn_max_deg == 0 || max_w <= 0x7fffffffffffffffull / (uint64_t)ctx->pn_max_deg, GG_EINVAL,
-             "%s: the largest weight %llu times the largest degree %d does not fit in 63 bits", fn, (unsigned long long)max_w, ctx->pn_max_deg);
+    GG_HIP(ctx, hipSetDevice(ctx->device));
+    rc = ensure_set_adjacency(ctx);
+    if (rc == GG_OK) rc = check_weight_bound(ctx, fn, weights, (int64_t)n_w * n);
+    if (rc != GG_OK) return rc;
 
-    const int64_t *hp = ctx->h_pn_ptr.data();
+    const int64_t *hp = ctx->set.h_ptr.data();
     const int pass = (int)std::min<int64_t>(m, PN_PASS);
     ScopedBuf d_u, d_v, d_cn, d_du, d_dv, d_ws, d_w, d_task;
     hipError_t e = d_u.reserve(sizeof(int32_t) * pass);
@@ -211,24 +193,13 @@ extern "C" int gg_pair_neighbors(gg_ctx *ctx, const int32_t *u, const int32_t *v
     double ms_total = 0.0;
     for (int64_t p0 = 0; p0 < m; p0 += pass) {
         const int cr = (int)std::min<int64_t>(pass, m - p0);
-        // the pass's tasks, ordered by group width
-        int64_t first[4] = {0, 0, 0, 0};
-        for (int i = 0; i < cr; ++i) {
+        // the pass's tasks over the pairs' shorter lists, ordered by group width; an empty list has its task too: it stores the outputs
+        int64_t first[4];
+        const auto shorter = [&](int i) {
             const int a = u[p0 + i], b = v[p0 + i];
-            const int s = (int)std::min(hp[a + 1] - hp[a], hp[b + 1] - hp[b]);
-            first[width_class(s) + 1] += s > PN_CHUNK ? cdiv(s, PN_CHUNK) : 1;
-        }
-        for (int c = 0; c < 3; ++c) first[c + 1] += first[c];
-        GG_CHECK(ctx, first[3] <= 0x7fffffffLL, GG_EINVAL, "%s: %lld tasks in one pass", fn, (long long)first[3]);
-        task.resize((size_t)first[3]);
-        int64_t fill[3] = {first[0], first[1], first[2]};
-        for (int i = 0; i < cr; ++i) {
-            const int a = u[p0 + i], b = v[p0 + i];
-            const int s = (int)std::min(hp[a + 1] - hp[a], hp[b + 1] - hp[b]);
-            const int c = width_class(s);
-            task[(size_t)fill[c]++] = make_int2(i, 0);
-            for (int c0 = PN_CHUNK; c0 < s; c0 += PN_CHUNK) task[(size_t)fill[c]++] = make_int2(i, c0);
-        }
+            return std::min(hp[a + 1] - hp[a], hp[b + 1] - hp[b]);
+        };
+        GG_CHECK(ctx, plan_width_tasks(cr, shorter, {8, 64}, PN_CHUNK, true, task, first), GG_EINVAL, "%s: %lld tasks in one pass", fn, (long long)first[3]);
         e = d_task.reserve(sizeof(int2) * task.size());
         if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %s", fn, hipGetErrorString(e));
         GG_HIP_FN(hipMemcpyAsync(d_u.p, u + p0, sizeof(int32_t) * cr, hipMemcpyHostToDevice, ctx->stream));
@@ -236,19 +207,10 @@ extern "C" int gg_pair_neighbors(gg_ctx *ctx, const int32_t *u, const int32_t *v
         GG_HIP_FN(hipMemcpyAsync(d_task.p, task.data(), sizeof(int2) * task.size(), hipMemcpyHostToDevice, ctx->stream));
         GG_HIP_FN(hipMemsetAsync(d_cn.p, 0, sizeof(int32_t) * cr, ctx->stream));  // (the chunk tasks of the long pairs add)
         if (n_w) GG_HIP_FN(hipMemsetAsync(d_ws.p, 0, sizeof(uint64_t) * (size_t)n_w * cr, ctx->stream));
-        PnArgs o{d_u.as<int32_t>(), d_v.as<int32_t>(), cr, nullptr, 0, ctx->pn_ptr.as<int64_t>(), ctx->pn_adj.as<int32_t>(), d_w.as<uint64_t>(), n_w, n,
+        PnArgs o{d_u.as<int32_t>(), d_v.as<int32_t>(), cr, nullptr, 0, ctx->set.ptr.as<int64_t>(), ctx->set.adj.as<int32_t>(), d_w.as<uint64_t>(), n_w, n,
                  d_cn.as<int32_t>(), d_du.as<int32_t>(), d_dv.as<int32_t>(), d_ws.as<unsigned long long>()};
         (void)hipEventRecord(ctx->ev0, ctx->stream);
-        for (int c = 0; c < 3; ++c) {
-            o.task = d_task.as<int2>() + first[c];
-            o.n_task = (int)(first[c + 1] - first[c]);
-            if (o.n_task == 0) continue;
-            const int W = c == 0 ? 4 : c == 1 ? 16 : 64;
-            const dim3 grid(std::min(PN_BLOCKS, cdiv(o.n_task, 256 / W)));
-            if (c == 0) hipLaunchKernelGGL(pn_sweep_kernel<4>, grid, dim3(256), 0, ctx->stream, o);
-            else if (c == 1) hipLaunchKernelGGL(pn_sweep_kernel<16>, grid, dim3(256), 0, ctx->stream, o);
-            else hipLaunchKernelGGL(pn_sweep_kernel<64>, grid, dim3(256), 0, ctx->stream, o);
-        }
+        launch_width_classes(ctx->stream, PN_BLOCKS, d_task.as<int2>(), first, o, pn_sweep_kernel<4>, pn_sweep_kernel<16>, pn_sweep_kernel<64>);
         (void)hipEventRecord(ctx->ev1, ctx->stream);
         GG_HIP_FN(hipGetLastError());
         GG_HIP_FN(hipMemcpyAsync(cn + p0, d_cn.p, sizeof(int32_t) * cr, hipMemcpyDeviceToHost, ctx->stream));

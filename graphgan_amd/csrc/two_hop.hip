@@ -6,11 +6,10 @@
 //
 // Shape (the first build; what was not tuned is listed in DESIGN.md "Two-hop sweep").  The host plans per query from the host
 // copy of the set adjacency: T(u) = sum over w in N(u) of deg(w), the entries of the expansion.  One workgroup per query:
-//   fill        an open-addressing (column + 1, uint64 sum) table of the power of two >= 2 min(T, n_node) slots (at least 256):
-//               a slot is claimed by compare-and-swap and its value added with a 64-bit integer atomic, linear probing from
-//               column mod slots -- cm_mode_table_kernel's scheme with a 64-bit value.  T <= TH_LDS_CAP = 2048: the table lies
+//   fill        a (column, uint64 sum) SetTable (set_sweep.h) for min(T, n_node) entries.  T <= TH_LDS_CAP = 2048: the table lies
 //               in LDS (4096 slots x 12 B = 48 KiB, with the selection's buffers 52 KiB: three workgroups share a CU's
-//               160 KiB); above, in a zeroed table of the context's scratch buffer, the queries batched under scratch_bytes.
+//               160 KiB); above, in a zeroed table of the context's scratch buffer (per task the values, then the keys), the
+//               queries batched under scratch_bytes.
 //               Lists N(w) of up to TH_NARROW = 64 entries are walked by groups of 16 lanes (16 lists at a time), longer ones
 //               by all 256 lanes of the workgroup: no list is truncated and no lane walks a hub's list alone;
 //   rank        the target's slot is looked up, then the table is scanned once: eligibility is c != u, c != v plus, under
@@ -26,7 +25,7 @@
 // not on the request, the grid, the batches, the order of the inserts or the run.
 #include <algorithm>
 
-#include "gg_internal.h"
+#include "set_sweep.h"
 
 namespace gg {
 
@@ -34,7 +33,6 @@ namespace {
 
 constexpr int TH_LDS_CAP = 2048;      // expansion entries T the LDS table takes (Engine.TWO_HOP_LDS_CAP); larger queries use global memory
 constexpr int TH_LDS_SLOTS = 2 * TH_LDS_CAP;
-constexpr int TH_MIN_SLOTS = 256;
 constexpr int TH_MAX_K = 256;         // list length at most: the survivors are sorted by one workgroup of 256 threads
 constexpr int TH_NARROW = 64;         // a list N(w) up to this length is walked by a 16-lane group, a longer one by the workgroup
 constexpr int TH_BLOCKS = 2048;       // workgroups per launch at most; they stride over the tasks behind them
@@ -65,51 +63,12 @@ struct ThArgs {
 };
 
 template <bool GLOBAL>
-struct ThTab {
-    uint32_t *key;
-    unsigned long long *val;
-    uint32_t mask;
-    __device__ __forceinline__ uint32_t ld_key(uint32_t s) const { return GLOBAL ? __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : key[s]; }
-    __device__ __forceinline__ unsigned long long ld_val(uint32_t s) const {
-        return GLOBAL ? __hip_atomic_load(val + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : val[s];
-    }
-    __device__ __forceinline__ void clear_val(uint32_t s) const {
-        if (GLOBAL) __hip_atomic_store(val + s, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else val[s] = 0ull;
-    }
-    // at most min(T, n_node) distinct columns in >= twice as many slots: a free or matching slot is always met
-    __device__ __forceinline__ void add(int c, unsigned long long wv) const {
-        const uint32_t k = (uint32_t)c + 1u;  // 0 marks an empty slot
-        uint32_t s = (uint32_t)c & mask;
-        for (;;) {
-            const uint32_t old = atomicCAS(key + s, 0u, k);
-            if (old == 0u || old == k) break;
-            s = (s + 1u) & mask;
-        }
-        atomicAdd(val + s, wv);
-    }
-    // the value under column c, 0 where the expansion never reached it (after the fill: read only)
-    __device__ __forceinline__ unsigned long long find(int c) const {
-        const uint32_t k = (uint32_t)c + 1u;
-        uint32_t s = (uint32_t)c & mask;
-        for (;;) {
-            const uint32_t kk = ld_key(s);
-            if (kk == 0u) return 0ull;
-            if (kk == k) return ld_val(s);
-            s = (s + 1u) & mask;
-        }
-    }
-};
+using ThTab = SetTable<unsigned long long, GLOBAL>;  // at most min(T, n_node) distinct columns in >= twice as many slots
 
 // x in the sorted list A[0, len)
 __device__ __forceinline__ bool th_member(const int32_t *A, int len, int x) {
-    int lo = 0, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (A[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < len && A[lo] == x;
+    const int p = set_lower_bound(A, 0, len, x);
+    return p < len && A[p] == x;
 }
 
 // the expansion of u into the table; every thread of the workgroup calls it (barrier inside)
@@ -138,8 +97,7 @@ __device__ __forceinline__ void th_fill(const ThArgs &o, const ThTab<GLOBAL> &tb
             for (int e = tid; e < dw; e += 256) tb.add(o.adj[wb + e], wv);
         }
     }
-    if (GLOBAL) __threadfence();
-    __syncthreads();
+    tb.fill_done();
 }
 
 template <bool GLOBAL>
@@ -155,10 +113,7 @@ __global__ __launch_bounds__(256) void th_rank_kernel(ThArgs o) {
         tb.val = GLOBAL ? o.tab + tk.off : s_val;
         tb.key = GLOBAL ? (uint32_t *)(tb.val + tk.slots) : s_key;
         tb.mask = tk.slots - 1u;
-        if (!GLOBAL) {
-            for (uint32_t s = tid; s < tk.slots; s += 256) s_key[s] = 0u, s_val[s] = 0ull;
-            __syncthreads();
-        }
+        if (!GLOBAL) tb.clear_lds();
         const int64_t ub = o.ptr[u];
         const int du = (int)(o.ptr[u + 1] - ub);
         th_fill<GLOBAL>(o, tb, ub, du);
@@ -212,10 +167,7 @@ __global__ __launch_bounds__(256) void th_topk_kernel(ThArgs o) {
         tb.val = GLOBAL ? o.tab + tk.off : s_val;
         tb.key = GLOBAL ? (uint32_t *)(tb.val + tk.slots) : s_key;
         tb.mask = tk.slots - 1u;
-        if (!GLOBAL) {
-            for (uint32_t s = tid; s < tk.slots; s += 256) s_key[s] = 0u, s_val[s] = 0ull;
-            __syncthreads();
-        }
+        if (!GLOBAL) tb.clear_lds();
         const int64_t ub = o.ptr[u];
         const int du = (int)(o.ptr[u + 1] - ub);
         th_fill<GLOBAL>(o, tb, ub, du);
@@ -329,13 +281,6 @@ __global__ __launch_bounds__(256) void th_topk_kernel(ThArgs o) {
     }
 }
 
-// first id outside [0, n_node), or -1
-int64_t th_bad_id(const int32_t *ids, int64_t m, int n_node) {
-    for (int64_t i = 0; i < m; ++i)
-        if (ids[i] < 0 || ids[i] >= n_node) return i;
-    return -1;
-}
-
 // The sweep of one request: `rank` selects the outputs.  Queries go in chunks (bounded device memory for the outputs); within a
 // chunk the LDS-table queries are one launch and the global-table queries as many passes as scratch_bytes asks for (a pass takes
 // at least one query, whatever its table's size).
@@ -343,17 +288,12 @@ int th_run(gg_ctx *ctx, const char *fn, bool rank, const int32_t *u, const int32
            int32_t *out_col, uint64_t *out_score, uint64_t *score, int32_t *ahead, int32_t *n_pos, int32_t *pos_below, double *kernel_ms) {
     const int n = ctx->n_node;
     GG_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = ensure_set_adjacency(ctx);
+    int rc = ensure_set_adjacency(ctx);
+    if (rc == GG_OK && weights) rc = check_weight_bound(ctx, fn, weights, n);
     if (rc != GG_OK) return rc;
-    if (weights) {  // a sum has at most max(deg) terms: it must stay below 2^63
-        uint64_t max_w = 0;
-        for (int x = 0; x < n; ++x) max_w = std::max(max_w, weights[x]);
-        GG_CHECK(ctx, max_w == 0 || ctx->pn_max_deg == 0 || max_w <= 0x7fffffffffffffffull / (uint64_t)ctx->pn_max_deg, GG_EINVAL,
-                 "%s: the largest weight %llu times the largest degree %d does not fit in 63 bits", fn, (unsigned long long)max_w, ctx->pn_max_deg);
-    }
     const int64_t cap = scratch_bytes > 0 ? scratch_bytes : TH_SCRATCH;
-    const int64_t *hp = ctx->h_pn_ptr.data();
-    const int32_t *ha = ctx->h_pn_adj.data();
+    const int64_t *hp = ctx->set.h_ptr.data();
+    const int32_t *ha = ctx->set.h_adj.data();
     const int64_t chunk = rank ? std::min<int64_t>(m, 1 << 20) : std::min<int64_t>(m, std::max<int64_t>(1, TH_CHUNK_OUT / k));
     ScopedBuf d_u, d_v, d_w, d_task, d_col, d_sc, d_np, d_ah, d_below;
     hipError_t e = d_u.reserve(sizeof(int32_t) * (size_t)chunk);
@@ -391,11 +331,9 @@ int th_run(gg_ctx *ctx, const char *fn, bool rank, const int32_t *u, const int32
                 const int64_t T = expansion[(size_t)i];
                 const bool lds = T <= TH_LDS_CAP;
                 if (lds != (pass == 0)) continue;
-                int64_t slots = TH_MIN_SLOTS;
-                while (slots < 2 * std::min<int64_t>(T, n)) slots <<= 1;
                 ThTask &tk = task[(size_t)(lds ? n_lds++ : n_lds + n_glob++)];
                 tk.q = i;
-                tk.slots = (uint32_t)slots;
+                tk.slots = (uint32_t)set_table_slots(std::min<int64_t>(T, n));
             }
         pass_first.assign(1, n_lds);
         int64_t words = 0, max_words = 0;
@@ -411,18 +349,18 @@ int th_run(gg_ctx *ctx, const char *fn, bool rank, const int32_t *u, const int32
         }
         pass_first.push_back(cr);
         if (max_words) {
-            e = ctx->th_tab.reserve(sizeof(uint64_t) * (size_t)max_words);
+            e = ctx->set.th_tab.reserve(sizeof(uint64_t) * (size_t)max_words);
             if (e != hipSuccess) return fail(ctx, GG_ENOMEM, "%s: %lld bytes of table scratch: %s", fn, (long long)(max_words * 8), hipGetErrorString(e));
         }
         GG_HIP_FN(hipMemcpyAsync(d_u.p, u + p0, sizeof(int32_t) * cr, hipMemcpyHostToDevice, ctx->stream));
         if (rank) GG_HIP_FN(hipMemcpyAsync(d_v.p, v + p0, sizeof(int32_t) * cr, hipMemcpyHostToDevice, ctx->stream));
         GG_HIP_FN(hipMemcpyAsync(d_task.p, task.data(), sizeof(ThTask) * (size_t)cr, hipMemcpyHostToDevice, ctx->stream));
         ThArgs o{};
-        o.tab = ctx->th_tab.as<unsigned long long>();
+        o.tab = ctx->set.th_tab.as<unsigned long long>();
         o.u = d_u.as<int32_t>();
         o.v = d_v.as<int32_t>();
-        o.ptr = ctx->pn_ptr.as<int64_t>();
-        o.adj = ctx->pn_adj.as<int32_t>();
+        o.ptr = ctx->set.ptr.as<int64_t>();
+        o.adj = ctx->set.adj.as<int32_t>();
         o.w = weights ? d_w.as<unsigned long long>() : nullptr;
         o.excl = excl;
         o.k = k;
@@ -444,7 +382,7 @@ int th_run(gg_ctx *ctx, const char *fn, bool rank, const int32_t *u, const int32
             const int64_t t0 = pass_first[ps], t1 = pass_first[ps + 1];
             if (t1 == t0) continue;
             const int64_t used = task[(size_t)t1 - 1].off + task[(size_t)t1 - 1].slots + task[(size_t)t1 - 1].slots / 2;
-            GG_HIP_FN(hipMemsetAsync(ctx->th_tab.p, 0, sizeof(uint64_t) * (size_t)used, ctx->stream));
+            GG_HIP_FN(hipMemsetAsync(ctx->set.th_tab.p, 0, sizeof(uint64_t) * (size_t)used, ctx->stream));
             o.task = d_task.as<ThTask>() + t0;
             o.n_task = (int)(t1 - t0);
             const dim3 grid((unsigned)std::min<int64_t>(TH_BLOCKS, t1 - t0));
@@ -498,8 +436,8 @@ extern "C" int gg_two_hop_topk(gg_ctx *ctx, const int32_t *rows, int64_t n_rows,
     GG_CHECK(ctx, k >= 1 && k <= TH_MAX_K, GG_EINVAL, "%s: k = %d outside [1, %d]", fn, k, TH_MAX_K);
     if (n_rows == 0) return GG_OK;
     GG_CHECK(ctx, rows && out_col && out_score && n_pos, GG_EINVAL, "%s: rows, out_col, out_score and n_pos must not be NULL", fn);
-    const int64_t bad = th_bad_id(rows, n_rows, ctx->n_node);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: rows[%lld] = %d out of range [0, %d)", fn, (long long)bad, rows[bad], ctx->n_node);
+    const int rc2 = check_ids(ctx, fn, "rows", rows, n_rows);
+    if (rc2 != GG_OK) return rc2;
     return th_run(ctx, fn, false, rows, nullptr, n_rows, k, weights, exclude, scratch_bytes, out_col, out_score, nullptr, nullptr, n_pos, nullptr, kernel_ms);
 }
 
@@ -512,9 +450,8 @@ extern "C" int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u, const int32_t *v, 
     if (rc != GG_OK) return rc;
     if (m == 0) return GG_OK;
     GG_CHECK(ctx, u && v && score && ahead && n_pos && pos_below, GG_EINVAL, "%s: u, v, score, ahead, n_pos and pos_below must not be NULL", fn);
-    int64_t bad = th_bad_id(u, m, ctx->n_node);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: u[%lld] = %d out of range [0, %d)", fn, (long long)bad, u[bad], ctx->n_node);
-    bad = th_bad_id(v, m, ctx->n_node);
-    GG_CHECK(ctx, bad < 0, GG_EINVAL, "%s: v[%lld] = %d out of range [0, %d)", fn, (long long)bad, v[bad], ctx->n_node);
+    int rc2 = check_ids(ctx, fn, "u", u, m);
+    if (rc2 == GG_OK) rc2 = check_ids(ctx, fn, "v", v, m);
+    if (rc2 != GG_OK) return rc2;
     return th_run(ctx, fn, true, u, v, m, 1, weights, exclude, scratch_bytes, nullptr, nullptr, score, ahead, n_pos, pos_below, kernel_ms);
 }

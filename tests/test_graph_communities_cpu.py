@@ -62,7 +62,8 @@ def test_constants_and_audit_are_in_step_with_the_source():
     assert re.search(r"^AUDITED = .*\bcommunities\.o\b", mk, flags=re.M) and re.search(r"^OBJ = .*\bcommunities\.o\b", mk, flags=re.M)
     # ONE set of mode kernels: the side of a half-step is an argument, not a second kernel
     assert len(re.findall(r"^__global__ .*void cm_mode_\w+_kernel\(", src, flags=re.M)) == 2 and "side_h" in src
-    device = src[:src.index("int mode_class(")]  # the kernels: no floating point
+    device = src[:src.index("int mode_class(")]  # the kernels, and the whole header of their shared parts: no floating point
+    device += open(os.path.join(ROOT, "graphgan_amd", "csrc", "set_sweep.h")).read()
     assert not re.search(r"\b(float|double|fmaf?|__f\w+_rn)\b", device)
 
 

@@ -61,7 +61,8 @@ def test_constants_and_audit_are_in_step_with_the_source(gr):
     assert re.search(r"^two_hop\.o: AUDIT = 'th_\[a-z0-9_\]\*kernel' 4 ", mk, flags=re.M)  # rank and top-K, each with the table in LDS and global
     assert re.search(r"^AUDITED = .*\btwo_hop\.o\b", mk, flags=re.M) and re.search(r"^OBJ = .*\btwo_hop\.o\b", mk, flags=re.M)
     assert sorted(re.findall(r"^__global__ .*void (th_\w+_kernel)\(", src, flags=re.M)) == ["th_rank_kernel", "th_topk_kernel"]
-    device = src[:src.index("int64_t th_bad_id(")]  # the kernels: no floating point, no inline assembly
+    device = src[:src.index("int th_run(")]  # the kernels, and the whole header of their shared parts: no floating point, no inline assembly
+    device += open(os.path.join(ROOT, "graphgan_amd", "csrc", "set_sweep.h")).read()
     assert not re.search(r"\b(float|double|fmaf?|__f\w+_rn|asm)\b", device)
 
 
