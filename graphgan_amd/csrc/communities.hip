@@ -31,15 +31,6 @@ constexpr int CM_CHUNK = 512;        // entries of a node's list per task of gg_
 constexpr int CM_BLOCKS = 2048;      // workgroups per launch at most (8 per CU); the groups stride over the tasks behind them
 constexpr int CM_CLASSES = 5;        // W = 4, 16, 64, the LDS table, the global table
 
-__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {  // the MurmurHash3 finaliser
-    x ^= x >> 16;
-    x *= 0x85ebca6bu;
-    x ^= x >> 13;
-    x *= 0xc2b2ae35u;
-    x ^= x >> 16;
-    return x;
-}
-
 struct CmArgs {
     const int32_t *task;       // [n_task] request rows of this launch
     int n_task;

@@ -102,15 +102,27 @@ struct SetGraph {
     bool mode_valid = false;
     // scratch of the call in flight: the hubs' partial rows (graph_prop.hip), the global tables (communities.hip, two_hop.hip)
     DevBuf gp_stage, cm_tab, th_tab;
-    // a new graph (gg_set_graph_csr): the adjacency and every plan go, the plan and scratch buffers keep their capacity
+    // the undirected edge list E = {(a, b) : a < b, b in N(a)} in (a, b) order, int2 [und_m]: a function of the graph alone, built on
+    // first use behind the adjacency (ensure_undirected_edges, spanning_forest.hip)
+    DevBuf und;
+    int64_t und_m = 0;
+    bool und_valid = false;
+    // state of the spanning-forest call in flight (spanning_forest.hip): the component of every node, the hook pointers (ping-pong),
+    // the smallest key per component (8 B per node), the smallest id per component, the forest flags and the per-sweep counters
+    DevBuf sf_comp, sf_parent[2], sf_best, sf_minid, sf_forest, sf_cnt;
+    // a new graph (gg_set_graph_csr): the adjacency, the edge list and every plan go, the plan and scratch buffers keep their capacity
     void drop() {
         ptr.release();
         adj.release();
-        valid = sum_valid = mode_valid = false;
+        und.release();
+        und_m = 0;
+        valid = sum_valid = mode_valid = und_valid = false;
     }
     void release() {
         drop();
-        for (DevBuf *b : {&gp_task, &gp_hub, &cm_task, &cm_goff, &cm_etask, &gp_stage, &cm_tab, &th_tab}) b->release();
+        for (DevBuf *b : {&gp_task, &gp_hub, &cm_task, &cm_goff, &cm_etask, &gp_stage, &cm_tab, &th_tab, &sf_comp, &sf_parent[0], &sf_parent[1], &sf_best, &sf_minid,
+                          &sf_forest, &sf_cnt})
+            b->release();
     }
 };
 

@@ -1,6 +1,6 @@
 // set_sweep.h -- the parts the graph-only sweeps over the SET adjacency (gg::SetGraph, ensure_set_adjacency) share, written once
 // for their four users: pair_neighbors.hip (link indices), graph_prop.hip (neighbour sum, label spreading), communities.hip
-// (neighbour mode, label propagation, partition edges) and two_hop.hip (two-hop top-K and rank).
+// (neighbour mode, label propagation, partition edges) and two_hop.hip (two-hop top-K and rank); spanning_forest.hip takes the hash.
 // Device part: the open-addressing (id, integer value) table of the hash-accumulate sweeps and the lower-bound search of the
 // walk-the-shorter-list sweeps -- __forceinline__ throughout and integer only.  Host part: the task planner and the launcher of
 // the three group widths, and the argument checks with the texts the entry points share.
@@ -11,6 +11,17 @@
 #include "gg_internal.h"
 
 namespace gg {
+
+// The MurmurHash3 finaliser: the hash of the neighbour-mode ties and the label-propagation sides (communities.hip) and of the
+// default edge priorities of the spanning forest (spanning_forest.hip).
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
+}
 
 // Slots of a table that takes `entries` distinct ids: the smallest power of two >= max(256, 2 entries), so that a probe always
 // meets a free or a matching slot.

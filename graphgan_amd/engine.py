@@ -762,6 +762,56 @@ class Engine:
         res = self.partition_edges(_gcomm.check_assign("modularity", a, self.n_node, n_label), n_label)
         return _gcomm.modularity_from_counts(res["intra"], res["tot"])
 
+    def undirected_edges(self):
+        """The undirected edge list of the resident training graph (gg_undirected_edges): E = {(a, b) : a < b, b in N(a)} over
+        the neighbour SETS (those of ``pair_neighbors``: no duplicate, no self-loop), ordered by (a, b): int32 [m, 2].  Built once
+        per graph; ``set_graph_csr`` drops it."""
+        m = ctypes.c_int64()
+        self._ck(lib.gg_undirected_edges(self._ctx, ctypes.byref(m), None))
+        edges = np.empty((int(m.value), 2), dtype=np.int32)
+        if m.value:
+            self._ck(lib.gg_undirected_edges(self._ctx, ctypes.byref(m), _ptr(edges)))
+        return edges
+
+    def spanning_forest(self, seed=0, priority=None, sweeps=False):
+        """The minimum spanning forest of the resident training graph and its connected components (gg_spanning_forest): Boruvka
+        rounds on the device over ``undirected_edges()``.  Edge j has the key (priority[j] << 32) | j; ``priority``: an integer array
+        [m] with values in [0, 2^32), or None for fmix32(j ^ fmix32(seed ^ 0x53504C54)) (split.default_priorities).  Keys are
+        distinct, so the forest is unique: forest[j] = 1 exactly when Kruskal in ascending key order takes edge j, whatever the
+        grid or the run.  component[v] = the smallest node id of v's component.  Returns dict(forest uint8 [m], component int32
+        [n_node], m, n_forest, n_components (isolated nodes count), rounds, ms); with ``sweeps`` also sweep_live / sweep_hooks
+        int64 and sweep_ms float64, one entry per edge sweep (the rounds and the last sweep, which hooks nothing)."""
+        fn = "spanning_forest"
+        m = ctypes.c_int64()
+        self._ck(lib.gg_undirected_edges(self._ctx, ctypes.byref(m), None))
+        m = int(m.value)
+        prio = None
+        if priority is not None:
+            prio = np.asarray(priority)
+            if prio.shape != (m,) or prio.dtype.kind not in "iu":
+                raise ValueError("%s: priority must be a uint32 array [%d]" % (fn, m))
+            if m and (int(prio.min()) < 0 or int(prio.max()) > 0xFFFFFFFF):
+                raise ValueError("%s: priority must be a uint32 array [%d]: a value outside [0, 2^32)" % (fn, m))
+            prio = np.ascontiguousarray(prio, dtype=np.uint32)
+        forest = np.zeros(m, dtype=np.uint8)
+        component = np.empty(self.n_node, dtype=np.int32)
+        stats = np.zeros(4, dtype=np.int64)
+        cnt = np.full((_lib.SF_MAX_SWEEPS, 2), -1, dtype=np.int64) if sweeps else None
+        sms = np.full(_lib.SF_MAX_SWEEPS, -1.0, dtype=np.float64) if sweeps else None
+        ms = ctypes.c_double()
+        self._ck(lib.gg_spanning_forest(self._ctx, int(seed) & 0xFFFFFFFF, _ptr(prio), m, _ptr(forest), _ptr(component), _ptr(stats), _ptr(cnt), _ptr(sms),
+                                        ctypes.byref(ms)))
+        res = dict(forest=forest, component=component, m=int(stats[0]), n_forest=int(stats[1]), n_components=int(stats[2]), rounds=int(stats[3]), ms=ms.value)
+        if sweeps:
+            k = int((cnt[:, 0] >= 0).sum())
+            res.update(sweep_live=cnt[:k, 0].copy(), sweep_hooks=cnt[:k, 1].copy(), sweep_ms=sms[:k].copy())
+        return res
+
+    def connected_components(self):
+        """component[v] = the smallest node id of v's connected component in the resident training graph (an isolated node is its
+        own component): the ``component`` output of ``spanning_forest(seed=0)``, int32 [n_node]."""
+        return self.spanning_forest(seed=0)["component"]
+
     TWO_HOP_LDS_CAP = _lib.TWO_HOP_LDS_CAP  # expansion entries of a query the two-hop sweep accumulates in an LDS table (more: a table in global memory)
 
     def _two_hop_args(self, fn, weights, exclude, scratch_bytes):

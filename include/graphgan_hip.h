@@ -870,6 +870,55 @@ int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u /* [m] */, const int32_t *v /*
                     int32_t exclude, int64_t scratch_bytes, uint64_t *score /* [m] */, int32_t *ahead /* [m] */, int32_t *n_pos /* [m] */,
                     int32_t *pos_below /* [m] */, double *kernel_ms /* or NULL */);
 
+/* ---- spanning-forest sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * The undirected edge list of the resident training graph, its minimum spanning forest under distinct integer keys and its
+ * connected components -- what a train / test split needs to hold edges out without cutting the training graph apart
+ * (graphgan_amd/split.py).  All on the set adjacency of the pair-neighbour sweep (sorted, distinct, no self-loop).  Needs
+ * gg_set_graph_csr; no embedding table is read; every result is an integer.
+ *
+ * gg_undirected_edges: E = {(a, b) : a < b, b in N(a)} ordered by (a, b) ascending, j = 0 .. m - 1.  *m = |E|; edges int32 [m, 2]
+ * is filled where it is not NULL (call once with NULL for m).  The list is built once per graph behind the set adjacency, kept on
+ * the device and dropped by gg_set_graph_csr.
+ *   limits      m not NULL ("gg_undirected_edges: m must not be NULL"); a resident graph ("gg_undirected_edges: needs the
+ *               training graph (gg_set_graph_csr)"); "<fn>: the graph has <m> undirected edges, more than 2^31 - 1".
+ *
+ * gg_spanning_forest:
+ *   key(j)      = (uint64(prio[j]) << 32) | j, prio the caller's uint32 [m] array (n_prio = m, its length); with prio NULL (n_prio
+ *               is then not read) prio[j] = fmix32(j ^ fmix32(seed ^ 0x53504C54)), fmix32 the finaliser of the neighbour-mode
+ *               sweep above.  Keys are distinct by construction, whatever the priorities.
+ *   forest[j]   uint8 [m]: 1 exactly when Kruskal, taking the edges in ascending key order, takes edge j -- equivalently: no path
+ *               between its ends uses only edges of smaller key.  This is the unique minimum spanning forest under the keys.
+ *   component[v]  int32 [n_node]: the smallest node id of v's connected component; a node without an edge is its own component.
+ *   stats       int64 [4] = {m, n_forest = the forest's edges, n_components = n_node - n_forest (isolated nodes count), rounds}.
+ *   rounds      the Boruvka rounds that hooked at least one component.  A round: every current component takes its
+ *               minimum-key edge to another component, and all of those edges are applied at once.
+ *   forest and component may each be NULL (not computed / not copied).
+ *   sweep_counts (int64 [GG_SF_MAX_SWEEPS, 2] or NULL): per edge sweep -- the rounds and the last one, which hooks nothing --
+ *               (the edges between two components, the components hooked); -1 behind the last sweep.  sweep_ms (double
+ *               [GG_SF_MAX_SWEEPS] or NULL): HIP-event time of each sweep with its pointer jumps; -1 behind the last.
+ *   bit contract  integers only, and the forest is unique: the outputs are a function of the graph and the keys alone -- not of
+ *               the grid, the order of the atomics or the run.
+ *   shape       a round is two sweeps of one thread per edge.  sf_min: an edge between two components asks for the 64-bit
+ *               unsigned minimum of its key on best[component] of both ends (vector global atomics); the asks of a wavefront's
+ *               consecutive lanes for one component are folded into one, and an ask that a relaxed load shows cannot lower the
+ *               word is dropped.  sf_hook: the edge whose key is best[c] sets forest[j] and parent[c] = the other component; two
+ *               components that chose each other -- the only cycle distinct keys allow -- write parent[max] = min alone.  Each
+ *               root is written by exactly one edge.  The hooks are counted per wavefront into one device word, the one word that
+ *               crosses to the host per round.  Then parent <- parent[parent] in ceil(log2(components)) + 1 launches (a round may
+ *               hook a chain as long as the graph) and comp[v] = parent[comp[v]].  At the end the smallest id per component by a
+ *               32-bit integer minimum.  The loop ends at the first round that hooks nothing; nothing on the device loops on a
+ *               condition.  State buffers live in the context and keep their capacity across calls.
+ *   limits      stats not NULL ("gg_spanning_forest: stats must not be NULL"); "gg_spanning_forest: priority has <k> entries, the
+ *               graph has <m> undirected edges"; "gg_spanning_forest: needs the training graph (gg_set_graph_csr)"; GG_EINVAL,
+ *               nothing is launched.  More than ceil(log2(max(n_node, 2))) + 1 rounds cannot happen: GG_ECAPACITY,
+ *               "gg_spanning_forest: internal error: more than <k> rounds on <n> nodes".
+ * kernel_ms (may be NULL): HIP-event time of the whole forest on the context's stream, with its per-round read-backs. */
+#define GG_SF_MAX_SWEEPS 34
+int gg_undirected_edges(gg_ctx *ctx, int64_t *m, int32_t *edges /* [m, 2] or NULL */);
+int gg_spanning_forest(gg_ctx *ctx, uint32_t seed, const uint32_t *prio /* [m] or NULL */, int64_t n_prio, uint8_t *forest /* [m] or NULL */,
+                       int32_t *component /* [n_node] or NULL */, int64_t *stats /* [4] */, int64_t *sweep_counts /* [GG_SF_MAX_SWEEPS, 2] or NULL */,
+                       double *sweep_ms /* [GG_SF_MAX_SWEEPS] or NULL */, double *kernel_ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
