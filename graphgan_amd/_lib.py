@@ -35,6 +35,7 @@ NEIGHBOR_SUM_CHUNK = 512  # == GP_CHUNK of csrc/graph_prop.hip: a node with more
 NEIGHBOR_SUM_MAX_COL = 128  # == GP_MAX_COL: columns of a neighbour sum / classes of a label spreading at most
 NEIGHBOR_MODE_LDS_CAP = 2048  # == CM_LDS_CAP of csrc/communities.hip: a longer neighbour list is counted in a table in global memory, not in LDS
 TWO_HOP_LDS_CAP = 2048  # == TH_LDS_CAP of csrc/two_hop.hip: a query with more expansion entries accumulates in a table in global memory, not in LDS
+PPR_LDS_CAP = 1024  # == PPR_LDS_CAP of csrc/ppr_push.hip: a push sweep that may touch more nodes (E = min(n_node, 1 + 2^40 / kmin)) keeps its tables in global memory, not in LDS
 PARTITION_EDGES_CHUNK = 512  # == CM_CHUNK: a node with more neighbours is split into tasks of this many entries by gg_partition_edges
 SF_MAX_SWEEPS = 34  # == GG_SF_MAX_SWEEPS of include/graphgan_hip.h: rows of gg_spanning_forest's per-sweep outputs
 ERROR_NAMES = {GG_EINVAL: "GG_EINVAL", GG_ECAPACITY: "GG_ECAPACITY", GG_EHIP: "GG_EHIP", GG_ECOMM: "GG_ECOMM",
@@ -135,6 +136,8 @@ SIGNATURES = {
     "gg_spanning_forest": (ctypes.c_int, [_P, _u32, _P, _i64, _P, _P, _P, _P, _P, _P]),
     "gg_two_hop_topk": (ctypes.c_int, [_P, _P, _i64, _i32, _P, _i32, _i64, _P, _P, _P, _P]),
     "gg_two_hop_rank": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _i64, _P, _P, _P, _P, _P]),
+    "gg_ppr_topk": (ctypes.c_int, [_P, _P, _i64, _i32, _u32, _u64, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_ppr_rank": (ctypes.c_int, [_P, _P, _P, _i64, _u32, _u64, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "gg_pretrain_set_noise": (ctypes.c_int, [_P, _P]),
     "gg_pretrain_set_walk_bias": (ctypes.c_int, [_P, _u32, _u32, _u32]),

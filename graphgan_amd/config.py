@@ -165,6 +165,20 @@ engine_cluster_modularity = False
 engine_link_rank_graph_baseline = False
 engine_rec_graph_baseline = False
 engine_graph_rank_indices = ("cn", "aa", "ra")   # common neighbours, Adamic-Adar, resource allocation
+# rooted (personalised) PageRank as a further graph-only ranking baseline (evaluation/graph_ppr.py): the push sweep, gg_ppr_rank /
+# gg_ppr_topk -- the local push of Andersen, Chung & Lang in fixed-point integers, which looks past the two hops of the indices above.
+# Both knobs work under any app, need test_filename and write ONE line, computed at the first evaluation and repeated at every later one:
+#   engine_link_rank_ppr_baseline   "graph_rank:index=ppr MRR= MR= H@<K>= ... n= reach= alpha= eps= rounds= converged= residual=" behind
+#                                   the last graph_rank line (or where it would stand): rounds = the largest of any query, converged =
+#                                   the share of queries whose push ended before engine_ppr_max_rounds, residual = the mean mass not pushed
+#   engine_rec_ppr_baseline         "graph_rec:index=ppr P@<K>= R@<K>= ... alpha= eps=" behind the last graph_rec line
+# The three parameters are untuned: the customary restart probability, and a threshold that keeps a query's work below 2^40 / kmin =
+# 66 669 adjacency entries; they have been run on no dataset but the CA-GrQc fixture.
+engine_link_rank_ppr_baseline = False
+engine_rec_ppr_baseline = False
+engine_ppr_alpha = 0.15         # restart probability, quantised to 2^-16
+engine_ppr_eps = 1e-4           # push threshold per unit of degree, quantised to 2^-40 of the mass
+engine_ppr_max_rounds = 200     # synchronous rounds of a query at most
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

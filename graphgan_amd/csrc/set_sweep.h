@@ -1,6 +1,7 @@
 // set_sweep.h -- the parts the graph-only sweeps over the SET adjacency (gg::SetGraph, ensure_set_adjacency) share, written once
-// for their four users: pair_neighbors.hip (link indices), graph_prop.hip (neighbour sum, label spreading), communities.hip
-// (neighbour mode, label propagation, partition edges) and two_hop.hip (two-hop top-K and rank); spanning_forest.hip takes the hash.
+// for their users: pair_neighbors.hip (link indices), graph_prop.hip (neighbour sum, label spreading), communities.hip (neighbour
+// mode, label propagation, partition edges), two_hop.hip (two-hop top-K and rank) and ppr_push.hip (rooted PageRank by local push);
+// spanning_forest.hip takes the hash.  The consumers of a filled table that two_hop.hip and ppr_push.hip share: set_consume.h.
 // Device part: the open-addressing (id, integer value) table of the hash-accumulate sweeps and the lower-bound search of the
 // walk-the-shorter-list sweeps -- __forceinline__ throughout and integer only.  Host part: the task planner and the launcher of
 // the three group widths, and the argument checks with the texts the entry points share.
@@ -57,8 +58,8 @@ struct SetTable {
         if (GLOBAL) __hip_atomic_store(val + s, (V)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else val[s] = (V)0;
     }
-    // value[id] += v: the slot is claimed by compare-and-swap, the value added with an integer atomic
-    __device__ __forceinline__ void add(int id, V v) const {
+    // the slot of id, claimed by compare-and-swap where no thread has claimed it yet
+    __device__ __forceinline__ uint32_t claim(int id) const {
         const uint32_t k = (uint32_t)id + 1u;
         uint32_t s = (uint32_t)id & mask;
         for (;;) {
@@ -66,8 +67,10 @@ struct SetTable {
             if (old == 0u || old == k) break;
             s = (s + 1u) & mask;
         }
-        atomicAdd(val + s, v);
+        return s;
     }
+    // value[id] += v: the slot is claimed, the value added with an integer atomic
+    __device__ __forceinline__ void add(int id, V v) const { atomicAdd(val + claim(id), v); }
     // the value under id, 0 where no add named it (behind fill_done)
     __device__ __forceinline__ V find(int id) const {
         const uint32_t k = (uint32_t)id + 1u;
@@ -139,6 +142,17 @@ inline int check_ids(gg_ctx *ctx, const char *fn, const char *name, const int32_
     const int n = ctx->n_node;
     for (int64_t i = 0; i < m; ++i)
         GG_CHECK(ctx, ids[i] >= 0 && ids[i] < n, GG_EINVAL, "%s: %s[%lld] = %d out of range [0, %d)", fn, name, (long long)i, ids[i], n);
+    return GG_OK;
+}
+
+// the argument checks the entry points of the per-query sweeps (two_hop.hip, ppr_push.hip) share, in the order the header lists
+// their texts; m_name: "n_rows" or "m"
+inline int check_query_request(gg_ctx *ctx, const char *fn, int64_t m, const char *m_name, int exclude, int64_t scratch_bytes) {
+    GG_CHECK(ctx, ctx->g_rowptr, GG_EINVAL, "%s: needs the training graph (gg_set_graph_csr)", fn);
+    GG_CHECK(ctx, m >= 0, GG_EINVAL, "%s: %s = %lld is negative", fn, m_name, (long long)m);
+    GG_CHECK(ctx, m <= 0x7fffffffLL, GG_EINVAL, "%s: %s = %lld does not fit in 31 bits", fn, m_name, (long long)m);
+    GG_CHECK(ctx, exclude == 1 || exclude == 2, GG_EINVAL, "%s: exclude = %d is neither 1 (self) nor 2 (graph)", fn, exclude);
+    GG_CHECK(ctx, scratch_bytes >= 0, GG_EINVAL, "%s: scratch_bytes = %lld is negative", fn, (long long)scratch_bytes);
     return GG_OK;
 }
 

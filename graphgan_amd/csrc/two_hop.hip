@@ -12,20 +12,15 @@
 //               queries batched under scratch_bytes.
 //               Lists N(w) of up to TH_NARROW = 64 entries are walked by groups of 16 lanes (16 lists at a time), longer ones
 //               by all 256 lanes of the workgroup: no list is truncated and no lane walks a hub's list alone;
-//   rank        the target's slot is looked up, then the table is scanned once: eligibility is c != u, c != v plus, under
-//               exclude = 2, a binary search in the sorted N(u); n_pos, ahead and pos_below are counted with compares, folded
-//               per wavefront by shuffles and per workgroup through LDS;
-//   top-K       the scan zeroes the values of the ineligible entries in place and folds n_pos and the largest score; if
-//               n_pos > k a radix select on the composite key (score, ~column) -- 8 bits per pass from the first non-zero byte
-//               of the largest score down, an LDS histogram with integer adds, the bucket found by a workgroup scan -- ends at
-//               the first byte whose bucket holds exactly the entries still wanted; the min(k, n_pos) survivors are gathered
-//               into LDS and bitonic-sorted (score descending, column ascending).  Composite keys are distinct, so selection and
-//               order are exact.
+//   rank        set_rank_consume (set_consume.h, shared with the push sweep): the target's slot is looked up and the table is
+//               scanned once, counting n_pos, ahead and pos_below with compares;
+//   top-K       set_topk_consume: the ineligible entries are zeroed in place, a radix select on the composite key (score,
+//               ~column) finds the k-th largest, and the min(k, n_pos) survivors are bitonic-sorted in LDS.
 // Every sum is an integer and the order is total, so a query's outputs depend on the graph, the weights and the query alone --
 // not on the request, the grid, the batches, the order of the inserts or the run.
 #include <algorithm>
 
-#include "set_sweep.h"
+#include "set_consume.h"
 
 namespace gg {
 
@@ -34,6 +29,7 @@ namespace {
 constexpr int TH_LDS_CAP = 2048;      // expansion entries T the LDS table takes (Engine.TWO_HOP_LDS_CAP); larger queries use global memory
 constexpr int TH_LDS_SLOTS = 2 * TH_LDS_CAP;
 constexpr int TH_MAX_K = 256;         // list length at most: the survivors are sorted by one workgroup of 256 threads
+static_assert(TH_MAX_K == SET_MAX_K, "the shared top-K consumer sorts TH_MAX_K survivors");
 constexpr int TH_NARROW = 64;         // a list N(w) up to this length is walked by a 16-lane group, a longer one by the workgroup
 constexpr int TH_BLOCKS = 2048;       // workgroups per launch at most; they stride over the tasks behind them
 constexpr int64_t TH_SCRATCH = 256ll << 20;  // default cap on the global tables of one pass, bytes
@@ -64,12 +60,6 @@ struct ThArgs {
 
 template <bool GLOBAL>
 using ThTab = SetTable<unsigned long long, GLOBAL>;  // at most min(T, n_node) distinct columns in >= twice as many slots
-
-// x in the sorted list A[0, len)
-__device__ __forceinline__ bool th_member(const int32_t *A, int len, int x) {
-    const int p = set_lower_bound(A, 0, len, x);
-    return p < len && A[p] == x;
-}
 
 // the expansion of u into the table; every thread of the workgroup calls it (barrier inside)
 template <bool GLOBAL>
@@ -104,7 +94,6 @@ template <bool GLOBAL>
 __global__ __launch_bounds__(256) void th_rank_kernel(ThArgs o) {
     __shared__ uint32_t s_key[GLOBAL ? 1 : TH_LDS_SLOTS];
     __shared__ unsigned long long s_val[GLOBAL ? 1 : TH_LDS_SLOTS];
-    __shared__ int r_cnt[4][3];
     const int tid = threadIdx.x;
     for (int t = blockIdx.x; t < o.n_task; t += gridDim.x) {  // (block-uniform: the barriers below are reached by every thread)
         const ThTask tk = o.task[t];
@@ -117,48 +106,23 @@ __global__ __launch_bounds__(256) void th_rank_kernel(ThArgs o) {
         const int64_t ub = o.ptr[u];
         const int du = (int)(o.ptr[u + 1] - ub);
         th_fill<GLOBAL>(o, tb, ub, du);
-        const unsigned long long sv = tb.find(v);  // (the same probes in every thread)
-        int np = 0, ah = 0, below = 0;
-        for (uint32_t s = tid; s < tk.slots; s += 256) {
-            const uint32_t k = tb.ld_key(s);
-            if (k == 0u) continue;
-            const unsigned long long x = tb.ld_val(s);
-            const int c = (int)(k - 1u);
-            if (x == 0ull || c == u || c == v) continue;
-            if (o.excl == 2 && th_member(o.adj + ub, du, c)) continue;
-            ++np;
-            ah += x > sv || (x == sv && c < v);
-            below += c < v;
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            np += __shfl_xor(np, off, 64);
-            ah += __shfl_xor(ah, off, 64);
-            below += __shfl_xor(below, off, 64);
-        }
-        if ((tid & 63) == 0) r_cnt[tid >> 6][0] = np, r_cnt[tid >> 6][1] = ah, r_cnt[tid >> 6][2] = below;
-        __syncthreads();
+        unsigned long long sv;
+        int np, ah, below;
+        set_rank_consume<GLOBAL>(tb, tk.slots, u, v, o.adj + ub, du, o.excl, sv, np, ah, below);
         if (tid == 0) {
             o.score[i] = sv;
-            o.n_pos[i] = r_cnt[0][0] + r_cnt[1][0] + r_cnt[2][0] + r_cnt[3][0];
-            o.ahead[i] = r_cnt[0][1] + r_cnt[1][1] + r_cnt[2][1] + r_cnt[3][1];
-            o.pos_below[i] = r_cnt[0][2] + r_cnt[1][2] + r_cnt[2][2] + r_cnt[3][2];
+            o.n_pos[i] = np;
+            o.ahead[i] = ah;
+            o.pos_below[i] = below;
         }
         __syncthreads();  // (the next task clears the table and the fold words)
     }
-}
-
-// "a comes before b": score descending, column ascending
-__device__ __forceinline__ bool th_before(unsigned long long sa, uint32_t ca, unsigned long long sb, uint32_t cb) {
-    return sa > sb || (sa == sb && ca < cb);
 }
 
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void th_topk_kernel(ThArgs o) {
     __shared__ uint32_t s_key[GLOBAL ? 1 : TH_LDS_SLOTS];
     __shared__ unsigned long long s_val[GLOBAL ? 1 : TH_LDS_SLOTS];
-    __shared__ unsigned long long s_sc[TH_MAX_K], r_max[4], s_thr_hi;
-    __shared__ uint32_t s_cl[TH_MAX_K], s_hist[256], r_sum[4], s_thr_lo, s_rem, s_n, s_done;
     const int tid = threadIdx.x;
     for (int t = blockIdx.x; t < o.n_task; t += gridDim.x) {  // (block-uniform: the barriers below are reached by every thread)
         const ThTask tk = o.task[t];
@@ -171,112 +135,7 @@ __global__ __launch_bounds__(256) void th_topk_kernel(ThArgs o) {
         const int64_t ub = o.ptr[u];
         const int du = (int)(o.ptr[u + 1] - ub);
         th_fill<GLOBAL>(o, tb, ub, du);
-        // Every scan below gives slot s to thread s mod 256, so a thread reads back only the zeroes it stored itself.
-        uint32_t np = 0;
-        unsigned long long mx = 0ull;
-        for (uint32_t s = tid; s < tk.slots; s += 256) {
-            const uint32_t k = tb.ld_key(s);
-            if (k == 0u) continue;
-            const unsigned long long x = tb.ld_val(s);
-            if (x == 0ull) continue;
-            const int c = (int)(k - 1u);
-            if (c == u || (o.excl == 2 && th_member(o.adj + ub, du, c))) {
-                tb.clear_val(s);
-                continue;
-            }
-            ++np;
-            mx = max(mx, x);
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            np += __shfl_xor(np, off, 64);
-            mx = max(mx, (unsigned long long)__shfl_xor(mx, off, 64));
-        }
-        if ((tid & 63) == 0) r_sum[tid >> 6] = np, r_max[tid >> 6] = mx;
-        s_sc[tid] = 0ull;  // (padding: score 0, column -1 -- behind every survivor)
-        s_cl[tid] = 0xffffffffu;
-        if (tid == 0) s_thr_hi = 0ull, s_thr_lo = 0u, s_rem = (uint32_t)o.k, s_n = 0u, s_done = 0u;
-        __syncthreads();
-        np = r_sum[0] + r_sum[1] + r_sum[2] + r_sum[3];
-        mx = max(max(r_max[0], r_max[1]), max(r_max[2], r_max[3]));
-        if (np > (uint32_t)o.k) {  // (block-uniform) the k-th largest composite key, byte by byte from the top
-            for (int b = 4 + (63 - __clzll((long long)mx)) / 8; b >= 0; --b) {  // (mx > 0; bytes above b are zero in every score)
-                s_hist[tid] = 0u;
-                __syncthreads();  // (also: the threshold words of the pass before)
-                const unsigned long long thi = s_thr_hi;
-                const uint32_t tlo = s_thr_lo, rem = s_rem;
-                for (uint32_t s = tid; s < tk.slots; s += 256) {
-                    const uint32_t k = tb.ld_key(s);
-                    if (k == 0u) continue;
-                    const unsigned long long x = tb.ld_val(s);
-                    if (x == 0ull) continue;
-                    const uint32_t lo = ~(k - 1u);
-                    bool match;
-                    uint32_t byte;
-                    if (b >= 4) {
-                        const int sh = 8 * (b - 4);
-                        match = sh == 56 || (x >> (sh + 8)) == (thi >> (sh + 8));
-                        byte = (uint32_t)(x >> sh) & 255u;
-                    } else {
-                        const int sh = 8 * b;
-                        match = x == thi && (b == 3 || (lo >> (sh + 8)) == (tlo >> (sh + 8)));
-                        byte = (lo >> sh) & 255u;
-                    }
-                    if (match) atomicAdd(&s_hist[byte], 1u);
-                }
-                __syncthreads();
-                // thread t takes bucket 255 - t: an inclusive scan over the threads counts the entries in its bucket and above
-                const uint32_t h = s_hist[255 - tid];
-                uint32_t incl = h;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t y = __shfl_up(incl, off, 64);
-                    if ((tid & 63) >= off) incl += y;
-                }
-                if ((tid & 63) == 63) r_sum[tid >> 6] = incl;
-                __syncthreads();
-                for (int w = 0; w < (tid >> 6); ++w) incl += r_sum[w];
-                if (incl >= rem && incl - h < rem) {  // (one thread: the bucket that holds the rem-th largest)
-                    const uint32_t bucket = 255u - (uint32_t)tid, left = rem - (incl - h);
-                    if (b >= 4) s_thr_hi = thi | ((unsigned long long)bucket << (8 * (b - 4)));
-                    else s_thr_lo = tlo | (bucket << (8 * b));
-                    s_rem = left;
-                    s_done = h == left;  // the whole bucket survives: the bytes below stay zero
-                }
-                __syncthreads();
-                if (s_done) break;  // (block-uniform; the last byte always ends here: the keys are distinct)
-            }
-        }
-        const unsigned long long thi = s_thr_hi;
-        const uint32_t tlo = s_thr_lo;
-        for (uint32_t s = tid; s < tk.slots; s += 256) {
-            const uint32_t k = tb.ld_key(s);
-            if (k == 0u) continue;
-            const unsigned long long x = tb.ld_val(s);
-            if (x == 0ull) continue;
-            const uint32_t lo = ~(k - 1u);
-            if (x > thi || (x == thi && lo >= tlo)) {
-                const uint32_t p = atomicAdd(&s_n, 1u);
-                if (p < (uint32_t)TH_MAX_K) s_sc[p] = x, s_cl[p] = k - 1u;  // (p < min(k, n_pos) by the selection)
-            }
-        }
-        __syncthreads();
-        for (int k2 = 2; k2 <= TH_MAX_K; k2 <<= 1)
-            for (int j = k2 >> 1; j > 0; j >>= 1) {
-                const int p = tid ^ j;
-                if (p > tid) {
-                    const bool up = (tid & k2) == 0;
-                    const unsigned long long sa = s_sc[tid], sb = s_sc[p];
-                    const uint32_t ca = s_cl[tid], cb = s_cl[p];
-                    if (th_before(sb, cb, sa, ca) == up) s_sc[tid] = sb, s_cl[tid] = cb, s_sc[p] = sa, s_cl[p] = ca;
-                }
-                __syncthreads();
-            }
-        if (tid < o.k) {
-            o.out_col[(int64_t)i * o.k + tid] = (int32_t)s_cl[tid];
-            o.out_score[(int64_t)i * o.k + tid] = s_sc[tid];
-        }
-        if (tid == 0) o.n_pos[i] = (int32_t)np;
+        set_topk_consume<GLOBAL>(tb, tk.slots, u, o.adj + ub, du, o.excl, o.k, (int64_t)i, o.out_col, o.out_score, o.n_pos);
         __syncthreads();  // (the next task clears the table, the list and the fold words)
     }
 }
@@ -409,16 +268,6 @@ int th_run(gg_ctx *ctx, const char *fn, bool rank, const int32_t *u, const int32
     return GG_OK;
 }
 
-// the argument checks the two entry points share, in the order the header lists their texts
-int th_check(gg_ctx *ctx, const char *fn, int64_t m, const char *m_name, int exclude, int64_t scratch_bytes) {
-    GG_CHECK(ctx, ctx->g_rowptr, GG_EINVAL, "%s: needs the training graph (gg_set_graph_csr)", fn);
-    GG_CHECK(ctx, m >= 0, GG_EINVAL, "%s: %s = %lld is negative", fn, m_name, (long long)m);
-    GG_CHECK(ctx, m <= 0x7fffffffLL, GG_EINVAL, "%s: %s = %lld does not fit in 31 bits", fn, m_name, (long long)m);
-    GG_CHECK(ctx, exclude == 1 || exclude == 2, GG_EINVAL, "%s: exclude = %d is neither 1 (self) nor 2 (graph)", fn, exclude);
-    GG_CHECK(ctx, scratch_bytes >= 0, GG_EINVAL, "%s: scratch_bytes = %lld is negative", fn, (long long)scratch_bytes);
-    return GG_OK;
-}
-
 }  // namespace
 
 }  // namespace gg
@@ -431,7 +280,7 @@ extern "C" int gg_two_hop_topk(gg_ctx *ctx, const int32_t *rows, int64_t n_rows,
     const char *fn = "gg_two_hop_topk";
     if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
     if (kernel_ms) *kernel_ms = 0.0;
-    const int rc = th_check(ctx, fn, n_rows, "n_rows", exclude, scratch_bytes);
+    const int rc = check_query_request(ctx, fn, n_rows, "n_rows", exclude, scratch_bytes);
     if (rc != GG_OK) return rc;
     GG_CHECK(ctx, k >= 1 && k <= TH_MAX_K, GG_EINVAL, "%s: k = %d outside [1, %d]", fn, k, TH_MAX_K);
     if (n_rows == 0) return GG_OK;
@@ -446,7 +295,7 @@ extern "C" int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u, const int32_t *v, 
     const char *fn = "gg_two_hop_rank";
     if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
     if (kernel_ms) *kernel_ms = 0.0;
-    const int rc = th_check(ctx, fn, m, "m", exclude, scratch_bytes);
+    const int rc = check_query_request(ctx, fn, m, "m", exclude, scratch_bytes);
     if (rc != GG_OK) return rc;
     if (m == 0) return GG_OK;
     GG_CHECK(ctx, u && v && score && ahead && n_pos && pos_below, GG_EINVAL, "%s: u, v, score, ahead, n_pos and pos_below must not be NULL", fn);

@@ -18,6 +18,7 @@ from .evaluation import link_heuristics as _lheur
 from .evaluation import label_propagation as _lprop
 from .evaluation import graph_communities as _gcomm
 from .evaluation import graph_ranking as _grank
+from .evaluation import graph_ppr as _gppr
 
 
 def _ptr(a):
@@ -867,6 +868,61 @@ class Engine:
             self._set_adj = _lheur.csr_set_adjacency(self._rowptr, self._col)
         rank, n_cand = _grank.full_rank(self._set_adj[0], self._set_adj[1], u_a, v_a, code, score, ahead, n_pos, pos_below)
         return dict(rank=rank, n_cand=n_cand, score=score, ahead=ahead, n_pos=n_pos, pos_below=pos_below, ms=ms.value)
+
+    PPR_LDS_CAP = _lib.PPR_LDS_CAP  # touched nodes E = min(n_node, 1 + 2^40 / kmin) up to which the push sweep keeps its tables in LDS (more: global memory)
+
+    def _ppr_args(self, fn, alpha, eps, max_rounds, exclude, scratch_bytes):
+        alpha_q, eps_q = _gppr.quantise(alpha, eps)
+        return alpha_q, eps_q, _gppr.check_max_rounds(fn, max_rounds), _grank.check_exclude(fn, exclude), _grank.check_scratch(fn, scratch_bytes)
+
+    def ppr_topk(self, rows, k=10, alpha=0.15, eps=1e-4, max_rounds=200, exclude=True, scratch_bytes=None):
+        """The push sweep's lists (gg_ppr_topk; evaluation/graph_ppr.py): for each query node rows[i] the first ``k`` (<= 256)
+        eligible candidates c with p[c] > 0, p the rooted PageRank of rows[i] on the neighbour SETS of the resident training graph
+        by the synchronous local push in fixed-point integers (2^40 = all the mass), score descending, column ascending.
+        ``alpha``: the restart probability, ``eps``: the push threshold per unit of degree, both quantised by
+        ``graph_ppr.quantise``; ``max_rounds``: the rounds of a query at most.  ``exclude`` and ``scratch_bytes`` as
+        ``two_hop_topk``'s.  All integer: a rerun and permuted, repeated or subset queries return the same bits per query.
+        Returns dict(col int32 [m, k] padded with -1, score uint64 [m, k] padded with 0, n_pos int32 [m], rounds int32 [m] = the
+        rounds that pushed, converged int32 [m], residual uint64 [m] = the mass not yet pushed, ms)."""
+        fn = "ppr_topk"
+        alpha_q, eps_q, max_rounds, code, scratch = self._ppr_args(fn, alpha, eps, max_rounds, exclude, scratch_bytes)
+        k = _grank.check_k(fn, k)
+        rows_a = _i32(_grank.check_ids(fn, "rows", rows, self.n_node))
+        m = len(rows_a)
+        col = np.full((m, k), -1, dtype=np.int32)
+        score = np.zeros((m, k), dtype=np.uint64)
+        n_pos, rounds, converged = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        residual = np.zeros(m, dtype=np.uint64)
+        ms = ctypes.c_double()
+        if m:
+            self._ck(lib.gg_ppr_topk(self._ctx, _ptr(rows_a), m, k, alpha_q, eps_q, max_rounds, code, scratch, _ptr(col), _ptr(score), _ptr(n_pos), _ptr(rounds),
+                                     _ptr(converged), _ptr(residual), ctypes.byref(ms)))
+        return dict(col=col, score=score, n_pos=n_pos, rounds=rounds, converged=converged, residual=residual, ms=ms.value)
+
+    def ppr_rank(self, u, v, alpha=0.15, eps=1e-4, max_rounds=200, exclude=True, scratch_bytes=None):
+        """The push sweep's ranks (gg_ppr_rank; evaluation/graph_ppr.py): for each query (u[i], v[i]) the position of v in
+        ``ppr_topk``'s order of root u over ALL candidates, the contract of ``two_hop_rank`` with S = p.  Queries with equal u that
+        stand next to each other share one push (sort by u to use it); a query's outputs depend on its own (u, v) alone.
+        Returns dict(rank int64 [m] (1 = best), n_cand int64 [m], score uint64 [m] = p[v], ahead, n_pos, pos_below int32 [m],
+        rounds, converged int32 [m], residual uint64 [m], ms)."""
+        fn = "ppr_rank"
+        alpha_q, eps_q, max_rounds, code, scratch = self._ppr_args(fn, alpha, eps, max_rounds, exclude, scratch_bytes)
+        u_a, v_a = _i32(_grank.check_ids(fn, "u", u, self.n_node)), _i32(_grank.check_ids(fn, "v", v, self.n_node))
+        if len(u_a) != len(v_a):
+            raise ValueError("%s: u and v must have the same length, got %d and %d" % (fn, len(u_a), len(v_a)))
+        m = len(u_a)
+        score, residual = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)
+        ahead, n_pos, pos_below, rounds, converged = (np.zeros(m, dtype=np.int32) for _ in range(5))
+        out = dict(score=score, ahead=ahead, n_pos=n_pos, pos_below=pos_below, rounds=rounds, converged=converged, residual=residual)
+        if not m:
+            return dict(rank=np.zeros(0, dtype=np.int64), n_cand=np.zeros(0, dtype=np.int64), ms=0.0, **out)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_ppr_rank(self._ctx, _ptr(u_a), _ptr(v_a), m, alpha_q, eps_q, max_rounds, code, scratch, _ptr(score), _ptr(ahead), _ptr(n_pos),
+                                 _ptr(pos_below), _ptr(rounds), _ptr(converged), _ptr(residual), ctypes.byref(ms)))
+        if self._set_adj is None:
+            self._set_adj = _lheur.csr_set_adjacency(self._rowptr, self._col)
+        rank, n_cand = _grank.full_rank(self._set_adj[0], self._set_adj[1], u_a, v_a, code, score, ahead, n_pos, pos_below)
+        return dict(rank=rank, n_cand=n_cand, ms=ms.value, **out)
 
     def graph_softmax(self, slots, for_d=False, nodes=None, q3_store=False):
         """The generator's distribution G(v | root) of the tree in each slot, exactly (gg_graph_softmax): the law of the end node

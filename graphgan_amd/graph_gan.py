@@ -57,6 +57,7 @@ from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
 from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
 from graphgan_amd.evaluation import graph_communities as gcomm  # noqa: E402
 from graphgan_amd.evaluation import graph_ranking as grank  # noqa: E402
+from graphgan_amd.evaluation import graph_ppr as gppr  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -134,6 +135,24 @@ def _check_graph_ranking(cfg):
         if not path or not os.path.isfile(path):
             raise ValueError("%s needs test edges: config.test_filename does not exist (%r)" % (knob, path))
         cls(cfg.train_filename, path, 1, indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES), ks=tuple(_cfg(cfg, ks_name, ks_default)))
+
+
+def _ppr_kw(cfg):
+    return dict(alpha=_cfg(cfg, "engine_ppr_alpha", gppr.DEFAULT_ALPHA), eps=_cfg(cfg, "engine_ppr_eps", gppr.DEFAULT_EPS),
+                max_rounds=_cfg(cfg, "engine_ppr_max_rounds", gppr.DEFAULT_MAX_ROUNDS))
+
+
+def _check_graph_ppr(cfg):
+    """the rooted-PageRank lines need the test edges, under any app, parameters inside the rule's ranges and the K of their evaluators
+    (checked before anything is computed)"""
+    for knob, ks_name, ks_default, cls in (("engine_link_rank_ppr_baseline", "engine_link_rank_ks", lrank.DEFAULT_KS, gppr.GraphPprRankEval),
+                                           ("engine_rec_ppr_baseline", "engine_rec_ks", (2, 10, 20), gppr.GraphPprRecEval)):
+        if not _cfg(cfg, knob, False):
+            continue
+        path = getattr(cfg, "test_filename", None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("%s needs test edges: config.test_filename does not exist (%r)" % (knob, path))
+        cls(cfg.train_filename, path, 1, ks=tuple(_cfg(cfg, ks_name, ks_default)), **_ppr_kw(cfg))
 
 
 def _check_link_rank(cfg):
@@ -593,6 +612,7 @@ class GraphGAN(object):
         _check_nc_graph_baseline(cfg)
         _check_cluster_graph_baseline(cfg)
         _check_graph_ranking(cfg)
+        _check_graph_ppr(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -724,21 +744,32 @@ class GraphGAN(object):
                                                seed=self.seed)
                 self._graph_cluster_line = gcomm.format_results(gce.eval_graph_communities())
             results.append(self._graph_cluster_line)
-        if _cfg(cfg, "engine_link_rank_graph_baseline", False) or _cfg(cfg, "engine_rec_graph_baseline", False):
-            # the ranking evaluators' graph-only lines (gg_two_hop_rank / gg_two_hop_topk): per index of engine_graph_rank_indices,
-            # "graph_rank:index=<i> MRR=<m> MR=<r> H@1=<h> ... n=<n> reach=<r>" and "graph_rec:index=<i> P@2=<p> R@2=<r> ..." --
-            # computed once and repeated, like graph_lp (without an engine: numpy on the training file, the same strings)
-            kw = dict(engine=self.engine, indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES))
-            if _cfg(cfg, "engine_link_rank_graph_baseline", False):
-                if getattr(self, "_graph_rank_lines", None) is None:
-                    self._graph_rank_lines = grank.GraphRankEval(cfg.train_filename, cfg.test_filename, self.n_node,
-                                                                 ks=tuple(_cfg(cfg, "engine_link_rank_ks", lrank.DEFAULT_KS)), **kw).lines()
-                results.extend(self._graph_rank_lines)
-            if _cfg(cfg, "engine_rec_graph_baseline", False):
-                if getattr(self, "_graph_rec_lines", None) is None:
-                    self._graph_rec_lines = grank.GraphRecEval(cfg.train_filename, cfg.test_filename, self.n_node,
-                                                               ks=tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20))), **kw).lines()
-                results.extend(self._graph_rec_lines)
+        # The ranking evaluators' graph-only lines, computed once and repeated, like graph_lp (without an engine: numpy on the training
+        # file, the same strings).  Two-hop sweep (gg_two_hop_rank / gg_two_hop_topk): per index of engine_graph_rank_indices,
+        # "graph_rank:index=<i> MRR=<m> MR=<r> H@1=<h> ... n=<n> reach=<r>" and "graph_rec:index=<i> P@2=<p> R@2=<r> ...".  Push sweep
+        # (gg_ppr_rank / gg_ppr_topk): "graph_rank:index=ppr ... alpha=<a> eps=<e> rounds=<r> converged=<c> residual=<r>" behind the last
+        # graph_rank line and "graph_rec:index=ppr ... alpha=<a> eps=<e>" behind the last graph_rec line, or where they would stand.
+        kw = dict(engine=self.engine, indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES))
+        if _cfg(cfg, "engine_link_rank_graph_baseline", False):
+            if getattr(self, "_graph_rank_lines", None) is None:
+                self._graph_rank_lines = grank.GraphRankEval(cfg.train_filename, cfg.test_filename, self.n_node,
+                                                             ks=tuple(_cfg(cfg, "engine_link_rank_ks", lrank.DEFAULT_KS)), **kw).lines()
+            results.extend(self._graph_rank_lines)
+        if _cfg(cfg, "engine_link_rank_ppr_baseline", False):
+            if getattr(self, "_graph_ppr_rank_lines", None) is None:
+                self._graph_ppr_rank_lines = gppr.GraphPprRankEval(cfg.train_filename, cfg.test_filename, self.n_node, engine=self.engine,
+                                                                   ks=tuple(_cfg(cfg, "engine_link_rank_ks", lrank.DEFAULT_KS)), **_ppr_kw(cfg)).lines()
+            results.extend(self._graph_ppr_rank_lines)
+        if _cfg(cfg, "engine_rec_graph_baseline", False):
+            if getattr(self, "_graph_rec_lines", None) is None:
+                self._graph_rec_lines = grank.GraphRecEval(cfg.train_filename, cfg.test_filename, self.n_node,
+                                                           ks=tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20))), **kw).lines()
+            results.extend(self._graph_rec_lines)
+        if _cfg(cfg, "engine_rec_ppr_baseline", False):
+            if getattr(self, "_graph_ppr_rec_lines", None) is None:
+                self._graph_ppr_rec_lines = gppr.GraphPprRecEval(cfg.train_filename, cfg.test_filename, self.n_node, engine=self.engine,
+                                                                 ks=tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20))), **_ppr_kw(cfg)).lines()
+            results.extend(self._graph_ppr_rec_lines)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -870,6 +870,67 @@ int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u /* [m] */, const int32_t *v /*
                     int32_t exclude, int64_t scratch_bytes, uint64_t *score /* [m] */, int32_t *ahead /* [m] */, int32_t *n_pos /* [m] */,
                     int32_t *pos_below /* [m] */, double *kernel_ms /* or NULL */);
 
+/* ---- push sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * Per query node u the rooted (personalised) PageRank of u on the set adjacency of the resident training graph -- N(x) and deg(x)
+ * are those of the pair-neighbour sweep (distinct entries, no self-loop) -- by the local push of Andersen, Chung & Lang, done
+ * synchronously in fixed-point integers, and from it the best k candidates or the place of one target: the graph-only baseline of
+ * the ranking evaluators that looks further than the two-hop sweep's two hops.  Needs gg_set_graph_csr; no embedding table is read;
+ * every result is an integer.  ONE = 2^40.
+ *   parameters  alpha_q in [1, 65535]: the restart probability in units of 2^-16;  eps_q in [1, 2^32]: the push threshold per unit
+ *               of degree, in units of 2^-40 of the mass;  alpha_q * eps_q >= 65536, so that kmin = (eps_q * alpha_q) >> 16 >= 1;
+ *               max_rounds >= 1.  With these ranges no product below reaches 2^63.
+ *   state       p[x] and r[x], unsigned 64-bit, all zero except r[u] = ONE.
+ *   a round     1. the active set is A = {x : r[x] > 0 and r[x] >= eps_q * max(deg(x), 1)};
+ *               2. if A is empty the query has converged and stops;
+ *               3. otherwise every x in A pushes simultaneously from its value r0 = r[x] at the START of the round:
+ *                    keep  = (r0 * alpha_q) >> 16, or keep = r0 where deg(x) = 0 (only the root can be such a node);
+ *                    rest  = r0 - keep;   share = rest / deg(x), integer division (0 for deg(x) = 0);   rem = rest - share * deg(x);
+ *                    p[x] += keep;   r[x] = rem + (what arrives this round);   r[w] += share for every w in N(x);
+ *               4. after max_rounds rounds the query stops unconverged.
+ *   outputs     the score S(u, c) = p[c];  rounds = the rounds that pushed;  converged = 1 if the active set after the last round
+ *               is empty;  residual = sum r.
+ *   invariants  sum p + sum r == ONE after every round.  Every push of x retires keep >= deg(x) * kmin, so over a whole query the
+ *               sum of deg(x) over all pushes is at most B = ONE / kmin, and at most E = min(n_node, 1 + B) distinct nodes are ever
+ *               touched.  rem < deg(x) <= eps_q * deg(x): a node that pushed is inactive until something arrives.
+ *   eligibility, order   those of the two-hop sweep: exclude = 1 ("self") or 2 ("graph"); score descending, column ascending;
+ *               zero-score nodes never enter a list.
+ *
+ * gg_ppr_topk: rows int32 [n_rows], ids may repeat; 1 <= k <= 256.  out_col / out_score / n_pos as gg_two_hop_topk's with S = p.
+ * gg_ppr_rank: queries (u[i], v[i]), i < m; score / ahead / n_pos / pos_below as gg_two_hop_rank's with S = p, and the rank follows
+ * on the host by the same full_rank.  Queries with equal u that stand next to each other in the request share one push and scan
+ * once per target; a query's outputs depend on its own (u, v) alone.
+ * Both: rounds int32, converged int32 and residual uint64, one per query.
+ *
+ *   bit contract  all adds are integer and the pushes of a round read start-of-round values only: a query's outputs are a function
+ *               of the graph, the parameters, exclude and the query alone.  A rerun, permuted, repeated or subset queries and any
+ *               scratch_bytes return the same bits per query.
+ *   shape       one workgroup of 256 threads per root.  One key array and two value arrays (r, p) over the slots of an
+ *               open-addressing table of set_table_slots(E) slots (the power of two >= max(256, 2 E)), the frontier as a list.
+ *               E <= 1024: everything lies in LDS; above, in zeroed scratch of the context.  Phase A: one thread per frontier
+ *               entry computes keep / share / rem.  Phase B: lists of up to 64 entries are walked by groups of 16 lanes, longer ones
+ *               by the whole workgroup; r[w] += share is a claim by compare-and-swap and a 64-bit integer atomic add whose returned
+ *               old value tells the one adder that crosses the threshold to append w to the next frontier.  The round count and
+ *               the frontier length stay on the device.  Then the two-hop sweep's consumers on (key, p).
+ *   scratch_bytes  the cap on the global-memory tables of one internal pass; 0 = the default (2 GiB).  A pass holds at least one
+ *               root whatever its tables' size.
+ *   limits      those of the two-hop sweep with its texts under the new names ("gg_ppr_topk: k = <k> outside [1, 256]",
+ *               "gg_ppr_topk: rows, out_col, out_score, n_pos, rounds, converged and residual must not be NULL",
+ *               "gg_ppr_rank: u, v, score, ahead, n_pos, pos_below, rounds, converged and residual must not be NULL"), and
+ *                 "<fn>: alpha_q = <a> outside [1, 65535]", "<fn>: eps_q = <e> outside [1, 4294967296]",
+ *                 "<fn>: max_rounds = <r> is below 1",
+ *                 "<fn>: alpha_q * eps_q = <product> is below 65536 (alpha_q = <a>, eps_q = <e>)";
+ *               nothing is launched.
+ * kernel_ms (may be NULL): HIP-event time of the sweep kernels and the table clears on the context's stream, summed over the
+ * internal passes.  Temporary device buffers are freed on every exit path. */
+int gg_ppr_topk(gg_ctx *ctx, const int32_t *rows /* [n_rows] */, int64_t n_rows, int32_t k, uint32_t alpha_q, uint64_t eps_q, int32_t max_rounds,
+                int32_t exclude, int64_t scratch_bytes, int32_t *out_col /* [n_rows, k] */, uint64_t *out_score /* [n_rows, k] */,
+                int32_t *n_pos /* [n_rows] */, int32_t *rounds /* [n_rows] */, int32_t *converged /* [n_rows] */, uint64_t *residual /* [n_rows] */,
+                double *kernel_ms /* or NULL */);
+int gg_ppr_rank(gg_ctx *ctx, const int32_t *u /* [m] */, const int32_t *v /* [m] */, int64_t m, uint32_t alpha_q, uint64_t eps_q, int32_t max_rounds,
+                int32_t exclude, int64_t scratch_bytes, uint64_t *score /* [m] */, int32_t *ahead /* [m] */, int32_t *n_pos /* [m] */,
+                int32_t *pos_below /* [m] */, int32_t *rounds /* [m] */, int32_t *converged /* [m] */, uint64_t *residual /* [m] */,
+                double *kernel_ms /* or NULL */);
+
 /* ---- spanning-forest sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
  * The undirected edge list of the resident training graph, its minimum spanning forest under distinct integer keys and its
  * connected components -- what a train / test split needs to hold edges out without cutting the training graph apart
