@@ -125,6 +125,7 @@ SIGNATURES = {
     "gg_topk_scores": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
     "gg_topk_metric": (ctypes.c_int, [_P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _P, _i64, _P, _P, _P]),
     "gg_rank_scores": (ctypes.c_int, [_P, _i32, _P, _P, _i64, _i32, _i32, _P, _P, _P, _P]),
+    "gg_top_pairs": (ctypes.c_int, [_P, _i32, _i32, _P, _i64, _i64, _i32, _i64, _P, _P, _P, _P, _P, _P]),
     "gg_distinct_degrees": (ctypes.c_int, [_P, _P]),
     "gg_pair_neighbors": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _P, _P, _P, _P, _P]),
     "gg_neighbor_sum": (ctypes.c_int, [_P, _P, _i32, _P, _P, _P, _i64, _P, _P]),

@@ -123,6 +123,20 @@ engine_nc_knn = False
 engine_knn_k = 10               # neighbours that vote, 1 .. 256
 engine_knn_metric = "cosine"    # "cosine" | "l2" | "dot"
 engine_knn_precision = "fp32"   # neighbour scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
+# global top-K pair prediction (evaluation/pair_prediction.py): ONE ranking over all pairs {u, v}, u < v, of the nodes with a training
+# edge by E[u] . E[v] (gg_top_pairs: a floor consumer on the tile stream; one call at max(engine_pair_ks) per line).  Both knobs work
+# under any app and write one line per mode after the *_knn lines and before graph_lp; no negatives file is read.
+#   engine_pair_prediction        "gen_pairs:P@<K>= R@<K>= ... n_test= dropped= n= found= precision=": the training edges are dropped
+#                                 from the ranking; are the best-scored non-edges the held-out edges?  Needs test_filename.  Positives:
+#                                 the distinct undirected test edges with both ends among those nodes that are no training edges or
+#                                 self-loops; dropped counts the other test edges.
+#   engine_graph_reconstruction   "gen_recon:P@<K>= R@<K>= ... edges= n= found= precision=": nothing is dropped; are the best-scored
+#                                 pairs the training edges (SDNE / HOPE precision@K)?
+# P@K = hits in the first min(K, found) entries / K, R@K = hits / positives.  The K are provisional: they have not been chosen on any dataset.
+engine_pair_prediction = False
+engine_graph_reconstruction = False
+engine_pair_ks = (100, 1000, 10000)  # positive integers <= 2^20
+engine_pair_precision = "fp32"       # pair scores in exact "fp32" or "bf16" (matrix-core bf16 inputs)
 # neighbourhood link-prediction baselines (evaluation/link_heuristics.py): with engine_lp_heuristics = True evaluation() appends, under
 # any app, after the *_knn lines and before gen_nll, ONE line "graph_lp:cn= jaccard= aa= ra= pa= n_test=" -- the AUC of common
 # neighbours, Jaccard, Adamic-Adar, resource allocation and preferential attachment on the TRAINING graph over the test edges and

@@ -608,6 +608,45 @@ class Engine:
                                         _ptr(rank), _ptr(n_cand), _ptr(score), ctypes.byref(ms)))
         return dict(rank=rank, n_cand=n_cand, score=score, kernel_ms=ms.value)
 
+    TOP_PAIRS_MAX_K = 1 << 20  # the limit of gg_top_pairs
+
+    def top_pairs(self, k, nodes=None, which=0, precision="fp32", exclude=True, buffer_entries=None):
+        """Global top-K pair prediction (gg_top_pairs): the ``k`` best-scored unordered pairs {u, v}, u < v, of ``nodes`` (None:
+        every node; else node ids, strictly ascending) under s(u, v) = E[u] . E[v] (no bias) of model ``which`` (0 = gen,
+        1 = dis) -- the bits ``rank(u, v, exclude=False)`` reports -- with ``exclude`` without the pairs whose v is a neighbour of
+        u in the resident training graph.  Order: score descending (-0 counts as +0), then (u, v) ascending.  precision "fp32"
+        (exact scores) or "bf16" (bf16 inputs, fp32 accumulate).  ``buffer_entries``: None the default max(2^22, 4 k), else the
+        device buffer's entries in [k + 4096, 2^26]; it changes no output but ``stats``.  One sweep of the tile stream; nothing
+        of size nodes x nodes is materialised.  Returns dict(u int32 [k], v int32 [k], score fp32 [k] (-1, -1, -inf behind
+        n_found), n_found = min(k, candidates), stats = dict(launches, retries, compactions, appended, compaction_ms,
+        buffer_entries), ms)."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("top_pairs: precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        if which not in (0, 1):
+            raise ValueError("top_pairs: which must be 0 (generator) or 1 (discriminator), got %r" % (which,))
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= self.TOP_PAIRS_MAX_K:
+            raise ValueError("top_pairs: k must be an integer in [1, 2^20], got %r" % (k,))
+        k = int(k)
+        if buffer_entries is not None and (isinstance(buffer_entries, bool) or int(buffer_entries) != buffer_entries
+                                           or not k + 4096 <= int(buffer_entries) <= 1 << 26):
+            raise ValueError("top_pairs: buffer_entries must be None or an integer in [k + 4096, 2^26], got %r" % (buffer_entries,))
+        nodes_a = None if nodes is None else _i32(nodes).reshape(-1)
+        if nodes_a is not None and len(nodes_a) == 0:
+            nodes_a = np.zeros(1, dtype=np.int32)  # (an empty set still needs a pointer: NULL means "every node")
+        m = 0 if nodes is None else len(_i32(nodes).reshape(-1))
+        u = np.empty(k, dtype=np.int32)
+        v = np.empty(k, dtype=np.int32)
+        score = np.empty(k, dtype=np.float32)
+        n_found = ctypes.c_int64()
+        stats = np.zeros(6, dtype=np.int64)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_top_pairs(self._ctx, which, {"fp32": 0, "bf16": 1}[precision], _ptr(nodes_a), m, k, int(bool(exclude)),
+                                  0 if buffer_entries is None else int(buffer_entries), _ptr(u), _ptr(v), _ptr(score), ctypes.byref(n_found),
+                                  _ptr(stats), ctypes.byref(ms)))
+        return dict(u=u, v=v, score=score, n_found=int(n_found.value),
+                    stats=dict(launches=int(stats[0]), retries=int(stats[1]), compactions=int(stats[2]), appended=int(stats[3]),
+                               compaction_ms=stats[4] / 1000.0, buffer_entries=int(stats[5])), ms=ms.value)
+
     PAIR_NEIGHBORS_CHUNK = _lib.PAIR_NEIGHBORS_CHUNK  # entries of a pair's shorter neighbour list per task of the sweep (longer lists are split)
 
     def distinct_degrees(self):

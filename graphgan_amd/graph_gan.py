@@ -53,6 +53,7 @@ from graphgan_amd.evaluation import node_clustering as ncl  # noqa: E402
 from graphgan_amd.evaluation import node_silhouette as nsil  # noqa: E402
 from graphgan_amd.evaluation import embedding_spectrum as espec  # noqa: E402
 from graphgan_amd.evaluation import node_knn as nknn  # noqa: E402
+from graphgan_amd.evaluation import pair_prediction as ppair  # noqa: E402
 from graphgan_amd.evaluation import link_heuristics as lheur  # noqa: E402
 from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
 from graphgan_amd.evaluation import graph_communities as gcomm  # noqa: E402
@@ -190,6 +191,23 @@ def _check_emb_spectrum(cfg):
         raise ValueError("engine_emb_spectrum needs at least two nodes with a training edge: %r has %d" % (path, n))
 
 
+def _check_pair_prediction(cfg):
+    """the pair lines need the training edges, gen_pairs also the test edges, under any app (checked before anything is computed)"""
+    pairs, recon = _cfg(cfg, "engine_pair_prediction", False), _cfg(cfg, "engine_graph_reconstruction", False)
+    if not pairs and not recon:
+        return
+    name = "engine_pair_prediction" if pairs else "engine_graph_reconstruction"
+    path = getattr(cfg, "train_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("%s needs the training edges: config.train_filename does not exist (%r)" % (name, path))
+    if pairs:
+        path = getattr(cfg, "test_filename", None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("engine_pair_prediction needs test edges: config.test_filename does not exist (%r)" % (path,))
+    ppair.check_ks(_cfg(cfg, "engine_pair_ks", ppair.DEFAULT_KS))
+    ppair.check_precision(_cfg(cfg, "engine_pair_precision", "fp32"))
+
+
 def _check_node_knn(cfg):
     """the k-NN lines need the labels file, under any app, and at most as many neighbours as the split has training nodes (checked
     before anything is computed)"""
@@ -219,6 +237,7 @@ class GraphGAN(object):
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
+        _check_pair_prediction(cfg)
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
         _check_cluster_graph_baseline(cfg)
@@ -608,6 +627,7 @@ class GraphGAN(object):
         _check_node_clustering(cfg)
         _check_emb_spectrum(cfg)
         _check_node_knn(cfg)
+        _check_pair_prediction(cfg)
         _check_lp_heuristics(cfg)
         _check_nc_graph_baseline(cfg)
         _check_cluster_graph_baseline(cfg)
@@ -713,6 +733,23 @@ class GraphGAN(object):
                                        precision=_cfg(cfg, "engine_knn_precision", "fp32"),
                                        train_ratio=float(_cfg(cfg, "engine_nc_train_ratio", 0.9)), seed=self.seed)
                 results.append(nknn.format_results(cfg.modes[i], nke.eval_node_knn()))
+        if _cfg(cfg, "engine_pair_prediction", False) or _cfg(cfg, "engine_graph_reconstruction", False):
+            # the head of ONE ranking over all pairs of the nodes with a training edge (gg_top_pairs; one call at max(ks) per line):
+            # "gen_pairs:P@<k>=<p> R@<k>=<r> ... n_test=<t> dropped=<d> n=<m> found=<f> precision=<p>" (the training edges dropped, the
+            # held-out edges the positives), then "gen_recon:P@<k>=<p> R@<k>=<r> ... edges=<e> n=<m> found=<f> precision=<p>" (nothing
+            # dropped, the training edges the positives); without an engine: float64 numpy on the .emb text
+            ks = ppair.check_ks(_cfg(cfg, "engine_pair_ks", ppair.DEFAULT_KS))
+            evs = []
+            for i in range(2):
+                emd = None if self.engine is not None else utils.read_embeddings(cfg.emb_filenames[i], n_node=self.n_node, n_embed=cfg.n_emb)
+                evs.append(ppair.PairPredictionEval(cfg.train_filename, getattr(cfg, "test_filename", None), self.n_node, cfg.n_emb, engine=self.engine,
+                                                    emd=emd, which=i, ks=ks, precision=_cfg(cfg, "engine_pair_precision", "fp32")))
+            if _cfg(cfg, "engine_pair_prediction", False):
+                for i in range(2):
+                    results.append(ppair.format_pairs(cfg.modes[i], evs[i].eval_pair_prediction(), ks))
+            if _cfg(cfg, "engine_graph_reconstruction", False):
+                for i in range(2):
+                    results.append(ppair.format_recon(cfg.modes[i], evs[i].eval_graph_reconstruction(), ks))
         if _cfg(cfg, "engine_lp_heuristics", False):
             # neighbourhood baselines on the training graph (gg_pair_neighbors): ONE line, "graph_lp:cn=<auc> jaccard=<auc> aa=<auc>
             # ra=<auc> pa=<auc> n_test=<n>" -- the graph is the same for both tables and every evaluation, so the line is computed

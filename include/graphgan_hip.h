@@ -980,6 +980,48 @@ int gg_spanning_forest(gg_ctx *ctx, uint32_t seed, const uint32_t *prio /* [m] o
                        int32_t *component /* [n_node] or NULL */, int64_t *stats /* [4] */, int64_t *sweep_counts /* [GG_SF_MAX_SWEEPS, 2] or NULL */,
                        double *sweep_ms /* [GG_SF_MAX_SWEEPS] or NULL */, double *kernel_ms /* or NULL */);
 
+/* ---- pair consumer (additive entry point; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * gg_top_pairs: the k best-scored pairs of the WHOLE node set -- "which k pairs are the most likely missing edges" -- in one
+ * sweep of the matrix-core tile stream (gg_all_score_reduce, gg_topk_scores, gg_rank_scores, gg_silhouette): nothing of size
+ * rows x columns exists at any time.
+ *   inputs      which (0 = generator, 1 = discriminator); precision 0 fp32 / 1 bf16 (n_emb <= 512); nodes: NULL = every node
+ *               (m is not read), or m node ids, STRICTLY ascending (m may be 0); k in [1, 2^20]; exclude 0 / 1 (1 needs
+ *               gg_set_graph_csr); buffer_entries: 0 = the default max(2^22, 4 k), else in [k + 4096, 2^26].
+ *   candidates  the unordered pairs {u, v} of members of `nodes` with u < v, each once; with exclude = 1 without the pairs whose v
+ *               is in u's list of the resident training graph (duplicates and self-loops in a list are fine).  (u, u) is never a
+ *               candidate.
+ *   score       s(u, v) = E[u] . E[v], fp32, NO bias, u (the smaller id) the ROW and v the COLUMN of the tile stream: the bits
+ *               gg_rank_scores reports for (u, v) at that precision (precision 0: the k-ordered fmaf chain from 0.0 of gg_all_score;
+ *               precision 1: v_mfma_f32_32x32x16_bf16 on the bf16 copy).
+ *   order       (u, v) is ahead of (u', v') when ord(s) > ord(s'), or the ords are equal and (u, v) < (u', v') lexicographically;
+ *               ord is that of gg_topk_scores' key, -0 counts as +0.
+ *   results     u_out, v_out int32 [k], score_out fp32 [k]: the best pairs in that order; *n_found = min(k, candidates); the
+ *               entries behind n_found are -1, -1, -inf.  m < 2 gives n_found = 0, not an error.
+ *               stats (int64 [6] or NULL) = {launches, retries, compactions, appended entries, microseconds of host time in the
+ *               compactions, the buffer's entries}.  ms (or NULL): HIP-event time of the whole sweep on the context's stream,
+ *               with its read-backs and compactions (the bf16 copy excluded, as in gg_topk_scores).
+ *   bit contract  u, v, score and n_found are a function of the table, the set and the graph alone -- not of buffer_entries, the
+ *               grid, the order of the appends or the run.  Non-finite scores: unspecified.
+ *   shape       One floor triple (fs, fu, fv) in device memory: the k-th best pair known, below everything until k are known;
+ *               a kernel reads it once.  Per tile and lane 16 compares acc >= fs and one ballot; behind a hit the triple compare,
+ *               column > row, the set's bit of the column, the binary search of the exclusion, and an append of (score bits, u, v)
+ *               to a buffer with ONE integer atomic per wavefront on the fill counter -- it counts on past the capacity, the
+ *               stores do not.  A launch is a rectangle of 32-row tiles x a column range in multiples of 128; a row tile starts at
+ *               the 128-column tile of its smallest id.  One 4-byte read-back per launch; on overflow the counter is set back and
+ *               the rectangle rerun as two halves (rows first, then columns); the first rectangle holds at most buffer_entries - k
+ *               pairs, later ones double, up to 4 096 rows x all columns and 2^32 - 2^27 pairs (the counter has 32 bits).  A compaction
+ *               (on the host: a selection among at most buffer_entries triples; when the fill passes min(k + (buffer_entries - k) / 2,
+ *               max(3 k, 2^16)), and at the end, where the k best are sorted) keeps the k best and stores the k-th as the floor.
+ *   limits      GG_EINVAL, nothing is launched, the text names gg_top_pairs: "which must be 0 (generator) or 1 (discriminator)",
+ *               "precision must be 0 (fp32) or 1 (bf16)", "exclude must be 0 or 1", "k = <k> outside [1, 2^20]",
+ *               "buffer_entries = <b> outside [k + 4096, 2^26] (0: the default)", "exclude = 1 needs the training graph
+ *               (gg_set_graph_csr)", "bf16 supports n_emb <= 512 (got <d>)", "fp32 supports n_emb <= 1116 (got <d>)",
+ *               "nodes[<i>] = <id> out of range [0, <n>)", "nodes[<i>] = <id> is not above nodes[<i - 1>] = <id> (strictly
+ *               ascending ids)" (the FIRST bad index), "bad argument" (a NULL output). */
+int gg_top_pairs(gg_ctx *ctx, int32_t which, int32_t precision, const int32_t *nodes /* [m] or NULL */, int64_t m, int64_t k, int32_t exclude,
+                 int64_t buffer_entries, int32_t *u_out /* [k] */, int32_t *v_out /* [k] */, float *score_out /* [k] */, int64_t *n_found,
+                 int64_t *stats /* [6] or NULL */, double *ms /* or NULL */);
+
 /* sess.run(embedding_matrix) (graph_gan.py:298); which: 0 = generator, 1 = discriminator
  * (config.modes order, config.py:1).  out is [n_node, n_emb] fp32, unpadded. */
 int gg_get_embeddings(gg_ctx *ctx, int32_t which, float *out);
