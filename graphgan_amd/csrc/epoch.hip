@@ -165,6 +165,7 @@ int gg_epoch_add(gg_ctx *ctx, const int32_t *roots, int32_t n_roots, int32_t do_
 int gg_epoch_commit(gg_ctx *ctx, int32_t which, int64_t *n_out) {
     if (!ctx) return fail(nullptr, GG_EINVAL, "ctx is NULL");
     GG_CHECK(ctx, which == 0 || which == 1, GG_EINVAL, "gg_epoch_commit: which must be 0 (generator pairs) or 1 (discriminator rows)");
+    GG_CHECK(ctx, !ctx->h_rowptr.empty(), GG_EINVAL, "epoch: call gg_set_graph_csr first");  // (as every other call of an epoch answers)
     GG_HIP(ctx, hipSetDevice(ctx->device));
     discard_begun_walk(ctx);
     GG_HIP(ctx, hipStreamSynchronize(ctx->stream));
