@@ -137,6 +137,7 @@ SIGNATURES = {
     "gg_spanning_forest": (ctypes.c_int, [_P, _u32, _P, _i64, _P, _P, _P, _P, _P, _P]),
     "gg_two_hop_topk": (ctypes.c_int, [_P, _P, _i64, _i32, _P, _i32, _i64, _P, _P, _P, _P]),
     "gg_two_hop_rank": (ctypes.c_int, [_P, _P, _P, _i64, _P, _i32, _i64, _P, _P, _P, _P, _P]),
+    "gg_two_hop_top_pairs": (ctypes.c_int, [_P, _P, _i64, _i64, _P, _i32, _i64, _i64, _P, _P, _P, _P, _P, _P]),
     "gg_ppr_topk": (ctypes.c_int, [_P, _P, _i64, _i32, _u32, _u64, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P]),
     "gg_ppr_rank": (ctypes.c_int, [_P, _P, _P, _i64, _u32, _u64, _i32, _i32, _i64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gg_graph_softmax": (ctypes.c_int, [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P]),

@@ -193,6 +193,16 @@ engine_rec_ppr_baseline = False
 engine_ppr_alpha = 0.15         # restart probability, quantised to 2^-16
 engine_ppr_eps = 1e-4           # push threshold per unit of degree, quantised to 2^-40 of the mass
 engine_ppr_max_rounds = 200     # synchronous rounds of a query at most
+# graph-only global top-K pair baseline (evaluation/graph_pairs.py): what "the K pairs with the largest neighbourhood index" on the
+# training graph alone -- the two-hop pair sweep, gg_two_hop_top_pairs; no embedding takes part -- reach on the two protocols of the
+# *_pairs / *_recon lines, with their node set, positives and K (engine_pair_ks).  Both knobs work under any app and write one line
+# per index of engine_graph_rank_indices, behind the last graph_rec line (or where it would stand) and before gen_nll; the lines are
+# computed at the first evaluation and repeated at every later one.
+#   engine_pair_graph_baseline    "graph_pairs:index=<i> P@<K>= R@<K>= ... n_test= dropped= n= found=": the training edges are dropped
+#                                 from the ranking.  Needs test_filename.
+#   engine_recon_graph_baseline   "graph_recon:index=<i> P@<K>= R@<K>= ... edges= n= found=": nothing is dropped.
+engine_pair_graph_baseline = False
+engine_recon_graph_baseline = False
 # skip-gram pre-training from uniform or node2vec (p, q) random walks (graphgan_amd/pretrain.py): with engine_pretrain = True a missing
 # pretrain_emb_filename_* is produced on the device and written in the reference's .emb text before it is read
 engine_pretrain = False

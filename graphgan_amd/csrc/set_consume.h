@@ -1,5 +1,6 @@
-// set_consume.h -- the two consumers of a filled (column, uint64 score) SetTable (set_sweep.h), written once for the sweeps that
-// rank every node by an integer score of one query node u: two_hop.hip (the two-hop sweep) and ppr_push.hip (the push sweep).
+// set_consume.h -- the consumers of a filled (column, uint64 score) SetTable (set_sweep.h), written once for the sweeps that
+// rank every node by an integer score of one query node u: two_hop.hip (the two-hop sweep), ppr_push.hip (the push sweep) and
+// two_hop_pairs.hip (the two-hop pair sweep: the floor consumer).
 // Device code only, __forceinline__ and integer only; each function declares the LDS it needs itself, so a kernel that inlines
 // one gets exactly that consumer's buffers.  Every thread of the 256-thread workgroup calls them (barriers inside), behind the
 // table's fill_done.
@@ -11,7 +12,13 @@
 //                      byte of the largest score down, an LDS histogram with integer adds, the bucket found by a workgroup scan --
 //                      ends at the first byte whose bucket holds exactly the entries still wanted; the min(k, n_pos) survivors are
 //                      gathered into LDS and bitonic-sorted (score descending, column ascending).  Composite keys are distinct, so
-//                      selection and order are exact.
+//                      selection and order are exact;
+//   set_floor_consume  the table of source u is scanned once against ONE global floor (fs, fu, fv), the k-th best pair {u, v}, u < v,
+//                      known to the whole run: an entry (c, x) survives when x > 0, c > u, c has its bit in the set's bitmap
+//                      (instances with one), c is outside the sorted N(u) (exclude) and (x, u, c) is strictly ahead of the floor;
+//                      the survivors are appended as (score lo, score hi, u, c) to a global buffer with ONE integer atomic per
+//                      wavefront and scan step on the fill counter (ballot, popcount, prefix).  The counter keeps counting past
+//                      the capacity, the stores do not.  It needs no LDS.
 #pragma once
 #include "set_sweep.h"
 
@@ -179,6 +186,48 @@ __device__ __forceinline__ void set_topk_consume(const SetTable<unsigned long lo
         out_score[i * k_out + tid] = s_sc[tid];
     }
     if (tid == 0) n_pos[i] = (int32_t)np;
+}
+
+// The floor of a pair sweep and where its survivors go.  The floor is the k-th best pair known, (0, max, max) -- "nothing is
+// behind it": every score > 0 is ahead -- until k pairs are known; a kernel reads it once.
+struct SetFloor {
+    unsigned long long fs;
+    int fu, fv;
+    const uint32_t *member;  // [ceil(n_node / 32)] bit c: node c is in the set (instances with a bitmap)
+    uint32_t *fill;          // entries appended so far (counts on past cap)
+    uint32_t cap;
+    uint4 *buf;              // [cap] (score lo, score hi, u, v)
+};
+
+// Every entry (c, x) of source u's table that is a candidate pair {u, c} strictly ahead of the floor, appended to f.buf.  Nu / du:
+// the sorted N(u), searched under excl.  slots is a multiple of 256, so all 64 lanes of a wavefront take part in every ballot.
+template <bool GLOBAL, bool BM>
+__device__ __forceinline__ void set_floor_consume(const SetTable<unsigned long long, GLOBAL> &tb, uint32_t slots, int u, const int32_t *Nu, int du, int excl,
+                                                  const SetFloor &f) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t s0 = 0; s0 < slots; s0 += 256) {
+        const uint32_t s = s0 + threadIdx.x;
+        const uint32_t k = tb.ld_key(s);
+        unsigned long long x = 0ull;
+        int c = 0;
+        bool p = false;
+        if (k != 0u) {
+            x = tb.ld_val(s);
+            c = (int)(k - 1u);
+            p = x > 0ull && c > u && (x > f.fs || (x == f.fs && (u < f.fu || (u == f.fu && c < f.fv))));
+            if (BM && p) p = ((f.member[c >> 5] >> (c & 31)) & 1u) != 0u;
+            if (p && excl) p = !set_member(Nu, du, c);
+        }
+        const unsigned long long hit = __builtin_amdgcn_ballot_w64(p);
+        if (hit == 0ull) continue;  // (wavefront-uniform)
+        const uint32_t total = (uint32_t)__popcll(hit);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(hit >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hit, 0u));
+        uint32_t base = 0u;
+        if (lane == 0) base = atomicAdd(f.fill, total);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        const uint32_t at = base + before;
+        if (p && at < f.cap) f.buf[at] = make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)u, (uint32_t)c);
+    }
 }
 
 }  // namespace gg

@@ -908,6 +908,45 @@ class Engine:
         rank, n_cand = _grank.full_rank(self._set_adj[0], self._set_adj[1], u_a, v_a, code, score, ahead, n_pos, pos_below)
         return dict(rank=rank, n_cand=n_cand, score=score, ahead=ahead, n_pos=n_pos, pos_below=pos_below, ms=ms.value)
 
+    TWO_HOP_TOP_PAIRS_MAX_K = 1 << 20  # the limit of gg_two_hop_top_pairs
+
+    def two_hop_top_pairs(self, k, nodes=None, weights=None, exclude=True, scratch_bytes=None, buffer_entries=None):
+        """The two-hop pair sweep (gg_two_hop_top_pairs; evaluation/graph_pairs.py): the ``k`` (<= 2^20) best unordered pairs
+        {u, v}, u < v, of ``nodes`` (None: every node; else node ids, strictly ascending) under S(u, v) = sum over w in N(u) & N(v)
+        of weights[w] on the neighbour SETS of the resident training graph -- the ``cn`` / ``wsum`` of ``pair_neighbors``, the
+        score of ``two_hop_rank``; w ranges over the whole graph, only the endpoints are restricted by ``nodes`` -- with S > 0
+        and, with ``exclude`` True, without the pairs that are training edges (False keeps them: u < v rules out the self pair).
+        Order: score descending, then (u, v) ascending.  ``weights``: None (every weight 1) or [n_node] non-negative integers,
+        summed as unsigned 64-bit integers (max(weights) * max(deg) must fit in 63 bits).  ``scratch_bytes``: the cap on the
+        global-memory tables of one internal pass; ``buffer_entries``: the device buffer's entries, at least k + the most entries
+        one source can append (the refusal names the minimum); None: the defaults.  Neither changes an output but ``stats``.  All
+        integer: the graph-only line beside ``top_pairs``; no embedding table is read.  Returns dict(u int32 [k], v int32 [k],
+        score uint64 [k] (-1, -1, 0 behind n_found), n_found = min(k, candidates), stats = dict(launches, retries, compactions,
+        appended, swept, skipped), ms)."""
+        fn = "two_hop_top_pairs"
+        w, scratch = _grank.check_weights(fn, weights, self.n_node), _grank.check_scratch(fn, scratch_bytes)
+        k = _grank.check_pair_k(fn, k)
+        if not isinstance(exclude, (bool, np.bool_)):
+            raise ValueError("%s: exclude must be True or False, got %r" % (fn, exclude))
+        if buffer_entries is not None and (isinstance(buffer_entries, (bool, np.bool_)) or not isinstance(buffer_entries, (int, np.integer))
+                                           or int(buffer_entries) < 1):
+            raise ValueError("%s: buffer_entries must be None or a positive integer, got %r" % (fn, buffer_entries))
+        nodes_a = None if nodes is None else _i32(_grank.check_ascending_ids(fn, "nodes", nodes, self.n_node))
+        m = 0 if nodes_a is None else len(nodes_a)
+        if nodes_a is not None and m == 0:
+            nodes_a = np.zeros(1, dtype=np.int32)  # (an empty set still needs a pointer: NULL means "every node")
+        u = np.empty(k, dtype=np.int32)
+        v = np.empty(k, dtype=np.int32)
+        score = np.empty(k, dtype=np.uint64)
+        n_found = ctypes.c_int64()
+        stats = np.zeros(6, dtype=np.int64)
+        ms = ctypes.c_double()
+        self._ck(lib.gg_two_hop_top_pairs(self._ctx, _ptr(nodes_a), m, k, _ptr(w), int(bool(exclude)), scratch, 0 if buffer_entries is None else int(buffer_entries),
+                                          _ptr(u), _ptr(v), _ptr(score), ctypes.byref(n_found), _ptr(stats), ctypes.byref(ms)))
+        return dict(u=u, v=v, score=score, n_found=int(n_found.value),
+                    stats=dict(launches=int(stats[0]), retries=int(stats[1]), compactions=int(stats[2]), appended=int(stats[3]), swept=int(stats[4]),
+                               skipped=int(stats[5])), ms=ms.value)
+
     PPR_LDS_CAP = _lib.PPR_LDS_CAP  # touched nodes E = min(n_node, 1 + 2^40 / kmin) up to which the push sweep keeps its tables in LDS (more: global memory)
 
     def _ppr_args(self, fn, alpha, eps, max_rounds, exclude, scratch_bytes):

@@ -83,6 +83,23 @@ def check_ids(fn, name, ids, n_node):
     return a
 
 
+def check_pair_k(fn, k):
+    """the k of the two-hop pair sweep (graph_pairs.py, Engine.two_hop_top_pairs): an integer in [1, 2^20]"""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1 << 20:
+        raise ValueError("%s: k must be an integer in [1, 2^20], got %r" % (fn, k))
+    return int(k)
+
+
+def check_ascending_ids(fn, name, ids, n_node):
+    """ids in [0, n_node), strictly ascending -> int64 array (the node set of the two-hop pair sweep)"""
+    a = check_ids(fn, name, ids, n_node)
+    bad = np.flatnonzero(np.diff(a) <= 0)
+    if len(bad):
+        i = int(bad[0]) + 1
+        raise ValueError("%s: %s[%d] = %d is not above %s[%d] = %d (strictly ascending ids)" % (fn, name, i, a[i], name, i - 1, a[i - 1]))
+    return a
+
+
 def check_scratch(fn, scratch_bytes):
     if scratch_bytes is None:
         return 0

@@ -106,6 +106,21 @@ def undirected(edges):
     return {(min(int(e[0]), int(e[1])), max(int(e[0]), int(e[1]))) for e in edges if int(e[0]) != int(e[1])}
 
 
+def held_out_positives(test_edges, nodes, train_edges):
+    """The positives of pair prediction and the number of test edges dropped: a test edge counts once, as (min, max), if it is no
+    self-loop, both ends are in ``nodes`` and it is no training edge -> (set of (u, v), u < v; dropped).  The one rule of
+    ``PairPredictionEval`` and ``graph_pairs.GraphPairsEval``."""
+    member = set(np.asarray(nodes).tolist())
+    positives, dropped = set(), 0
+    for e in test_edges:
+        a, b = min(int(e[0]), int(e[1])), max(int(e[0]), int(e[1]))
+        if a == b or a not in member or b not in member or (a, b) in train_edges or (a, b) in positives:
+            dropped += 1
+        else:
+            positives.add((a, b))
+    return positives, dropped
+
+
 class PairPredictionEval(object):
     def __init__(self, train_filename, test_filename, n_node, n_emb, engine=None, emd=None, which=0, ks=DEFAULT_KS, precision="fp32"):
         """``engine`` (+ ``which``): Engine.top_pairs on the resident table and training graph; otherwise float64 numpy on ``emd``
@@ -133,15 +148,7 @@ class PairPredictionEval(object):
         """-> dict(pr {k: (P, R)}, n_test, dropped, n, found, precision)"""
         if self.test_filename is None:
             raise ValueError("pair prediction needs test edges")
-        test = utils.read_edges_from_file(self.test_filename)
-        member = set(self.nodes.tolist())
-        positives, dropped = set(), 0
-        for e in test:
-            a, b = min(int(e[0]), int(e[1])), max(int(e[0]), int(e[1]))
-            if a == b or a not in member or b not in member or (a, b) in self.train_edges or (a, b) in positives:
-                dropped += 1
-            else:
-                positives.add((a, b))
+        positives, dropped = held_out_positives(utils.read_edges_from_file(self.test_filename), self.nodes, self.train_edges)
         pairs, found = self._top(True)
         return dict(pr=precision_recall(pairs, positives, self.ks), n_test=len(positives), dropped=dropped, n=len(self.nodes), found=found,
                     precision=self.precision)

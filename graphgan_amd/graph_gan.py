@@ -59,6 +59,7 @@ from graphgan_amd.evaluation import label_propagation as lprop  # noqa: E402
 from graphgan_amd.evaluation import graph_communities as gcomm  # noqa: E402
 from graphgan_amd.evaluation import graph_ranking as grank  # noqa: E402
 from graphgan_amd.evaluation import graph_ppr as gppr  # noqa: E402
+from graphgan_amd.evaluation import graph_pairs as gpairs  # noqa: E402
 
 _OPTIMIZERS = {"adam_dense": _lib.GG_OPT_ADAM_DENSE, "adam_lazy": _lib.GG_OPT_ADAM_LAZY, "sgd": _lib.GG_OPT_SGD}
 
@@ -154,6 +155,24 @@ def _check_graph_ppr(cfg):
         if not path or not os.path.isfile(path):
             raise ValueError("%s needs test edges: config.test_filename does not exist (%r)" % (knob, path))
         cls(cfg.train_filename, path, 1, ks=tuple(_cfg(cfg, ks_name, ks_default)), **_ppr_kw(cfg))
+
+
+def _check_graph_pairs(cfg):
+    """the graph-only pair lines need the training edges, graph_pairs also the test edges, under any app, known indices and the K of
+    the pair lines (checked before anything is computed)"""
+    pairs, recon = _cfg(cfg, "engine_pair_graph_baseline", False), _cfg(cfg, "engine_recon_graph_baseline", False)
+    if not pairs and not recon:
+        return
+    name = "engine_pair_graph_baseline" if pairs else "engine_recon_graph_baseline"
+    path = getattr(cfg, "train_filename", None)
+    if not path or not os.path.isfile(path):
+        raise ValueError("%s needs the training edges: config.train_filename does not exist (%r)" % (name, path))
+    if pairs:
+        path = getattr(cfg, "test_filename", None)
+        if not path or not os.path.isfile(path):
+            raise ValueError("engine_pair_graph_baseline needs test edges: config.test_filename does not exist (%r)" % (path,))
+    grank.check_indices(_cfg(cfg, "engine_graph_rank_indices", grank.INDICES))
+    ppair.check_ks(_cfg(cfg, "engine_pair_ks", ppair.DEFAULT_KS))
 
 
 def _check_link_rank(cfg):
@@ -264,6 +283,8 @@ class GraphGAN(object):
         self._graph_cluster_line = None  # the graph_cluster results line (engine_cluster_graph_baseline) likewise
         self._graph_rank_lines = None  # the graph_rank / graph_rec results lines (engine_link_rank_graph_baseline, engine_rec_graph_baseline) likewise
         self._graph_rec_lines = None
+        self._graph_pairs_lines = None  # the graph_pairs / graph_recon results lines (engine_pair_graph_baseline, engine_recon_graph_baseline) likewise
+        self._graph_recon_lines = None
 
         self.seed = int(_cfg(cfg, "engine_seed", 0))
         # rows missing from the pre-trained file are drawn from the global numpy RNG (utils.py:63); the
@@ -633,6 +654,7 @@ class GraphGAN(object):
         _check_cluster_graph_baseline(cfg)
         _check_graph_ranking(cfg)
         _check_graph_ppr(cfg)
+        _check_graph_pairs(cfg)
         results = []
         if cfg.app == "link_prediction":
             for i in range(2):
@@ -807,6 +829,21 @@ class GraphGAN(object):
                 self._graph_ppr_rec_lines = gppr.GraphPprRecEval(cfg.train_filename, cfg.test_filename, self.n_node, engine=self.engine,
                                                                  ks=tuple(_cfg(cfg, "engine_rec_ks", (2, 10, 20))), **_ppr_kw(cfg)).lines()
             results.extend(self._graph_ppr_rec_lines)
+        # The pair lines' graph-only lines (gg_two_hop_top_pairs: the two-hop pair sweep; one call at max(engine_pair_ks) per index and
+        # line), computed once and repeated like the lines above: per index of engine_graph_rank_indices "graph_pairs:index=<i>
+        # P@<k>=<p> R@<k>=<r> ... n_test=<t> dropped=<d> n=<m> found=<f>", then "graph_recon:index=<i> P@<k>=<p> R@<k>=<r> ... edges=<e>
+        # n=<m> found=<f>" -- the node set, the positives and the scoring of the *_pairs / *_recon lines.
+        if _cfg(cfg, "engine_pair_graph_baseline", False) or _cfg(cfg, "engine_recon_graph_baseline", False):
+            gpe = gpairs.GraphPairsEval(cfg.train_filename, getattr(cfg, "test_filename", None), self.n_node, engine=self.engine,
+                                        indices=_cfg(cfg, "engine_graph_rank_indices", grank.INDICES), ks=_cfg(cfg, "engine_pair_ks", ppair.DEFAULT_KS))
+            if _cfg(cfg, "engine_pair_graph_baseline", False):
+                if getattr(self, "_graph_pairs_lines", None) is None:
+                    self._graph_pairs_lines = gpe.lines("pairs")
+                results.extend(self._graph_pairs_lines)
+            if _cfg(cfg, "engine_recon_graph_baseline", False):
+                if getattr(self, "_graph_recon_lines", None) is None:
+                    self._graph_recon_lines = gpe.lines("recon")
+                results.extend(self._graph_recon_lines)
         if _cfg(cfg, "engine_gen_nll", False):
             # held-out NLL of the generator's graph softmax (gg_graph_softmax): "gen_nll:NLL=<nll> reach=<reach> n=<n>"
             results.append(gl.format_line(self.gen_likelihood()))

@@ -870,6 +870,56 @@ int gg_two_hop_rank(gg_ctx *ctx, const int32_t *u /* [m] */, const int32_t *v /*
                     int32_t exclude, int64_t scratch_bytes, uint64_t *score /* [m] */, int32_t *ahead /* [m] */, int32_t *n_pos /* [m] */,
                     int32_t *pos_below /* [m] */, double *kernel_ms /* or NULL */);
 
+/* ---- two-hop pair sweep (additive entry point; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
+ * gg_two_hop_top_pairs: the k best pairs of the WHOLE node set by a neighbourhood index -- "the k most likely missing edges from an
+ * edge list alone" -- the graph-only line beside gg_top_pairs.  On the neighbour SETS N(x) of the resident training graph (the set
+ * adjacency of the two-hop sweep above: distinct entries, no self-loop).  Needs gg_set_graph_csr; no embedding table is read;
+ * every result is an integer.
+ *   score       S(u, v) = sum over w in N(u) & N(v) of weights[w], unsigned 64-bit; weights uint64 [n_node] or NULL = every weight
+ *               1.  The value gg_pair_neighbors and gg_two_hop_rank report for (u, v).  w ranges over the WHOLE graph; only the
+ *               endpoints are restricted by `nodes`.  max(weights) * max(deg) must fit in 63 bits (checked on the host).
+ *   candidates  the unordered pairs {u, v}, u < v, both in `nodes` (NULL = every node, m is not read; otherwise m ids, STRICTLY
+ *               ascending, m may be 0), with S(u, v) > 0 and, with exclude = 1, v not in N(u).  exclude = 0 keeps the edges: u < v
+ *               rules out the self pair, so nothing has to be refused.  Zero-score pairs never enter: they would fill the list by id.
+ *   order       score descending, then (u, v) ascending: total and integer.
+ *   results     out_u, out_v int32 [k], out_score uint64 [k]: the first k (1 <= k <= 2^20) candidates in that order; *n_found =
+ *               min(k, candidates); the entries behind n_found are -1, -1, 0.
+ *               stats (int64 [6] or NULL) = {launches (batches of sources, one read-back each), retries, compactions, entries
+ *               appended, sources swept, sources skipped by the bound}.  kernel_ms (or NULL): HIP-event time of the whole sweep on
+ *               the context's stream, with its table clears, read-backs and compactions.
+ *   bit contract  out_u, out_v, out_score and n_found are a function of the graph, the weights, nodes, k and exclude alone -- not of
+ *               buffer_entries, scratch_bytes, the grid, the source order, the batches or the run.
+ *   shape       One workgroup of 256 threads per source u.  Fill: the expansion of u restricted to the upper triangle -- for w in
+ *               N(u) the suffix of the sorted N(w) above u, found by one binary search per list -- into the two-hop sweep's
+ *               open-addressing (column, uint64 sum) table; the host plans the table from T'(u) = sum over w in N(u) of |{c in
+ *               N(w), c > u}|, computed exactly: T' <= 2048 the table lies in LDS, above in a zeroed table of the context's
+ *               scratch, the sources batched under scratch_bytes (0 = the default, 256 MiB; a pass holds at least one source).
+ *               Lists of up to 64 entries are walked by groups of 16 lanes, longer ones by the workgroup.  Consume: ONE floor
+ *               (fs 64 bits, fu, fv) in device memory, the k-th best pair known -- (0, max, max) until k are known -- read once
+ *               per kernel; one scan of the table keeps the entries (c, x) with x > 0, c > u, the set's bit of c, c outside N(u)
+ *               under exclude, and (x, u, c) strictly ahead of the floor, and appends them as (score lo, score hi, u, v) to a
+ *               buffer with ONE integer atomic per wavefront and scan step on the fill counter -- it counts on past the capacity,
+ *               the stores do not.  Host: the sources with T' > 0 go in descending B(u) = sum over w in N(u) of weights[w] (deg(u)
+ *               without weights), ties by id; S(u, .) <= B(u), so a source with B(u) < fs is not launched (counted in stats).  A
+ *               launch is a batch of consecutive sources, 256 at first, doubling to 65 536 while nothing overflows; one 4-byte
+ *               read-back per launch; on overflow the counter is set back, the buffer compacted if it holds more than k entries
+ *               and the batch rerun as two halves.  A compaction (on the host; when the fill passes min(k + (buffer_entries - k) /
+ *               2, max(3 k, 2^16)), and at the end, where the k best are sorted) keeps the k best and stores the k-th as the floor.
+ *   buffer_entries  0 = the default max(minimum, 2^22, 4 k), else in [minimum, max(2^26, minimum)], minimum = k + the largest
+ *               min(T'(u), members above u): one source always fits behind k entries.
+ *   limits      GG_EINVAL, nothing is launched, the text names gg_two_hop_top_pairs: "needs the training graph (gg_set_graph_csr)",
+ *               "k = <k> outside [1, 2^20]", "exclude = <e> is neither 0 nor 1", "scratch_bytes = <b> is negative",
+ *               "buffer_entries = <b> is negative", "out_u, out_v, out_score and n_found must not be NULL", "m = <m> is negative",
+ *               "nodes[<i>] = <id> out of range [0, <n>)", "nodes[<i>] = <id> is not above nodes[<i - 1>] = <id> (strictly
+ *               ascending ids)" (the FIRST bad index), "the largest weight <w> times the largest degree <d> does not fit in 63
+ *               bits", "buffer_entries = <b> outside [<minimum>, <maximum>] (0: the default; the minimum is k + <bound>, the most
+ *               entries one source can append)".  GG_ECAPACITY, nothing is launched: "one source reaches <e> nodes above it, more
+ *               than 2^30: its table has no 32-bit slot count" (min(T'(u), n_node - 1 - u) > 2^30), "one source can append <b>
+ *               entries: a buffer of more than 2^31 entries".  Temporary device buffers are freed on every exit path. */
+int gg_two_hop_top_pairs(gg_ctx *ctx, const int32_t *nodes /* [m] or NULL */, int64_t m, int64_t k, const uint64_t *weights /* [n_node] or NULL */,
+                         int32_t exclude, int64_t scratch_bytes, int64_t buffer_entries, int32_t *out_u /* [k] */, int32_t *out_v /* [k] */,
+                         uint64_t *out_score /* [k] */, int64_t *n_found, int64_t *stats /* [6] or NULL */, double *kernel_ms /* or NULL */);
+
 /* ---- push sweep (additive entry points; GG_ABI_VERSION stays 9: no existing symbol, struct or behaviour changes).
  * Per query node u the rooted (personalised) PageRank of u on the set adjacency of the resident training graph -- N(x) and deg(x)
  * are those of the pair-neighbour sweep (distinct entries, no self-loop) -- by the local push of Andersen, Chung & Lang, done
